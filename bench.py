@@ -25,6 +25,13 @@ and the binding's kind table; the cold leg rebuilds those too. Distinct shards a
 the bytes a step reads were last touched more than twice the 256 MiB Infinity Cache ago (the count
 is derived from the algorithmic bytes of one step, `--replicas` overrides). Per-rule counters are
 built once, after the timed region (kpe_fetch), not per step.
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit,
+ms_per_step, ...). `--dump-outputs DIR` also writes what the last timed step computed (kpe_fetch of
+its shard: the verdict matrix and the per-rule counters) as DIR/<name>.npy. `--full` adds every
+other leg after the timed region: the per-rule totals, the verdict gather, the per-kernel timing
+pass and roofline, the single-shard / masks / cold legs, the CPU baseline and the end-to-end
+ingestion, as further keys of the same line.
 """
 import math
 import argparse
@@ -59,6 +66,37 @@ def scan_accounting(launches, kernel_ms_sum, bytes_sum, steps, ms_per_step, repl
             "achieved_per_step_gbs": per_step / (ms_per_step * 1e-3) / 1e9 if ms_per_step > 0 else 0.0,
             # the bytes read between two uses of one shard (each step evaluates one shard)
             "rotated_scan_bytes": per_step * replicas}
+
+
+DUMP_CAP_BYTES = 48 << 20  # --dump-outputs: the verdict rows and their indices, of the 64 MB allowed in all
+DUMP_SEED = 0xD0
+
+
+def dump_rows(n, rules, cap_bytes=DUMP_CAP_BYTES):
+    """Rows of an n x rules matrix that --dump-outputs writes (float32 cells and a float64 index per
+    row): every row when they fit in cap_bytes, else a fixed seeded sample of the rows, ascending
+    (the same rows on every run)."""
+    import numpy as np
+
+    keep = cap_bytes // (4 * rules + 8)
+    if n <= keep:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, verdicts, counts):
+    """DIR/verdicts.npy (float32, rows dump_rows picks of the N x R kpe_verdict matrix),
+    DIR/verdict_rows.npy (float64, those rows' indices) and DIR/counts.npy (float64, R x 7 in
+    COUNT_FIELDS order): what kpe_fetch returned for the last timed step."""
+    import numpy as np
+
+    from kyverno_amd.shard import counts_to_rows
+
+    os.makedirs(out_dir, exist_ok=True)
+    rows = dump_rows(verdicts.shape[0], verdicts.shape[1])
+    np.save(os.path.join(out_dir, "verdicts.npy"), verdicts[rows].astype(np.float32))
+    np.save(os.path.join(out_dir, "verdict_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "counts.npy"), np.asarray(counts_to_rows(counts), dtype=np.float64).reshape(-1, 7))
 
 
 def cpu_budget():
@@ -142,12 +180,17 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one per GPU); without an external launcher "
                                                         "(WORLD_SIZE unset) bench.py starts them itself")
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", choices=("c2", "c3", "c4", "c5"), default="c2")
     ap.add_argument("--resources", type=int, default=0, help="rows per GPU (0 = the config's size)")
     ap.add_argument("--replicas", type=int, default=0, help="distinct shards rotated (0 = the config's default)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="rows in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (per-rule totals, gather, per-kernel "
+                         "timing and roofline, single-shard / masks / cold legs, CPU baseline, end-to-end ingestion)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (verdicts, per-rule counts) as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="--full: rows in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every CPU this process may use (cpu_budget)")
     ap.add_argument("--traffic-json", default="")
     ap.add_argument("--total-resources", type=int, default=0,
@@ -157,6 +200,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:  # no external launcher: start the ranks here
         return launch_ranks(args.gpus, sys.argv[1:] if argv is None else argv)
@@ -257,13 +302,14 @@ def main(argv=None):
     # the first binding of shard 0 (the end-to-end legs run after the timed region)
     eng.evaluate_async(ps, corpora[0])
     eng.device.sync()
-    # correctness touch + counters from one synchronous evaluation per replica
+    # --full: correctness touch + counters from one synchronous evaluation per replica
     totals = [dict.fromkeys(COUNT_FIELDS, 0) for _ in range(R)]
-    for c in corpora:
-        _, _, cnt = eng.evaluate(ps, c)
-        for r in range(R):
-            for f in COUNT_FIELDS:
-                totals[r][f] += cnt[r][f]
+    if args.full:
+        for c in corpora:
+            _, _, cnt = eng.evaluate(ps, c)
+            for r in range(R):
+                for f in COUNT_FIELDS:
+                    totals[r][f] += cnt[r][f]
 
     # warm-up: every shard at least once (first binding: program upload, prologue image, PSA
     # summaries), then W more steps
@@ -286,6 +332,35 @@ def main(argv=None):
     elapsed = time.perf_counter() - t0
     barrier()
     elapsed = max_over_ranks(elapsed, device=coll_dev)
+    ms_per_step = elapsed / args.steps * 1e3
+    value = float(n_all) * R * args.steps / elapsed
+    if args.dump_outputs and rank == 0:  # the last timed step's shard, as a caller reads it back
+        v_last, _, cnt_last = eng.fetch(ps, steps_batch.corpora[-1])
+        dump_outputs(args.dump_outputs, v_last, cnt_last)
+        del v_last
+    line = {
+        "metric": "resource-rule evals/sec, 1M Pods × PSS restricted, 1/8 GPU; % HBM BW",
+        "value": value,
+        "unit": "resource-rule evals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if args.total_resources else "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": f"synthetic (kpe_synth {cfg.upper()} generator, seed {seed:#x})",
+        "config": {"workload": workload, "resources_per_gpu": n, "rules": R, "global_resources": n_all,
+                   "replicas_rotated": replicas, "parallelism": f"resource-sharded x{world}",
+                   "infinity_cache_bytes": IC_BYTES},
+    }
+    if not args.full:  # a plain run ends here; everything below is --full
+        if rank == 0:
+            print(json.dumps(line))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # the exchanges, after the timed region: per-rule totals (R x 7 u64, one RCCL all-reduce over
     # xGMI) and the verdict matrix of each rank's first shard, packed on its GPU to 3-bit cells
     # and sent from HBM to rank 0 (grouped RCCL point-to-point: one send per rank, all receives
@@ -314,7 +389,6 @@ def main(argv=None):
     st = eng.device.kernel_stats(reset=True)
     single_stream_ms = (time.perf_counter() - t1) / args.steps * 1e3
     L = max(st.launches, 1)
-    ms_per_step = elapsed / args.steps * 1e3
     acct = scan_accounting(st.launches, st.pss_kernel_ms, st.scan_bytes_sum, args.steps, ms_per_step, replicas)
     step_bytes = acct["alg_bytes_per_step"]
     scan_ms = acct["kernel_ms"]
@@ -372,9 +446,6 @@ def main(argv=None):
     masks_batch_leg = leg(masks=True, batch=True)  # the same through the multi-shard launches
     cold_leg = leg(masks=True, cold=True)
     eng.device.set_timing(False)
-
-    evals = float(n_all) * R * args.steps
-    value = evals / elapsed
 
     traffic = None
     scan_kernel = SCAN_KERNELS.get(st.scan_kernel, "kpe_scan_kernel")
@@ -470,28 +541,15 @@ def main(argv=None):
         e2e_flat, e2e_up, t_eval1 = t1 - t0, t2 - t1, t3 - t2
         e2e_s = t3 - t0
         del nd0
-        line = {
-            "metric": "resource-rule evals/sec, 1M Pods × PSS restricted, 1/8 GPU; % HBM BW",
-            "value": value,
-            "unit": "resource-rule evals/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong" if args.total_resources else "weak",
-            "vs_baseline": None,
-            "dtype": "u32",
-            "data": f"synthetic (kpe_synth {cfg.upper()} generator, seed {seed:#x})",
-            "config": {"workload": workload, "resources_per_gpu": n, "rules": R, "global_resources": n_all,
-                       "replicas_rotated": replicas, "parallelism": f"resource-sharded x{world}",
-                       # scan bytes touched between two uses of one shard vs the Infinity Cache
-                       "rotated_scan_bytes": acct["rotated_scan_bytes"], "infinity_cache_bytes": IC_BYTES,
-                       "rotation_exceeds_infinity_cache": acct["rotated_scan_bytes"] >= 2 * IC_BYTES,
-                       # cells where the rule matched the resource (a RuleResponse exists), per s
-                       "matched_cell_evals_per_s": value * sum(n_all * replicas - totals[r]["na"]
-                                                               for r in range(R)) / float(n_all * replicas * R),
-                       "counts_rule0": totals[0]},
+        line["config"].update({
+            # scan bytes touched between two uses of one shard vs the Infinity Cache
+            "rotated_scan_bytes": acct["rotated_scan_bytes"],
+            "rotation_exceeds_infinity_cache": acct["rotated_scan_bytes"] >= 2 * IC_BYTES,
+            # cells where the rule matched the resource (a RuleResponse exists), per s
+            "matched_cell_evals_per_s": value * sum(n_all * replicas - totals[r]["na"]
+                                                    for r in range(R)) / float(n_all * replicas * R),
+            "counts_rule0": totals[0]})
+        line.update({
             "roofline": scan_roof,
             "cpu_baseline": cpu,
             "gather": gather,
@@ -507,7 +565,7 @@ def main(argv=None):
                     # evaluation at ~6 ms of a ~0.25 s shard there is nothing for the flatten to hide
                     # behind, and it measured the same as this serial leg, profiles/r06_d)
                     },
-        }
+        })
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

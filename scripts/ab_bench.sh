@@ -13,7 +13,7 @@ for spec in "$@"; do
   args=()
   [ "$envs" != "-" ] && IFS=, read -ra args <<< "$envs"
   echo "== $CFG $name ($(date +%T)) ${args[*]}"
-  env "${args[@]}" timeout -k 10 300 python bench.py --config "$CFG" --steps 20 --warmup 5 --cpu-sample 0 \
+  env "${args[@]}" timeout -k 10 300 python bench.py --full --config "$CFG" --steps 20 --warmup 5 --cpu-sample 0 \
     > "$O/ab_${CFG}_$name.log" 2>&1
   rc=$?
   echo "== rc=$rc"

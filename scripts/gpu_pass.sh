@@ -4,7 +4,9 @@
 # runs under its own time limit; the pass stops at the first failing step.
 #   smoke                 __graft_entry__.smoke()
 #   tests[:<pytest -k>]   the -m gpu suite (or the tests matching the -k expression), one process
-#   bench:<cfg>[:<args>]  bench.py --config <cfg> <args> (args: comma-separated) -> bench_<cfg>.json
+#   bench:<cfg>[:<args>]  bench.py --full --config <cfg> <args> (args: comma-separated) -> bench_<cfg>.json
+#                         (trace, pmc, traffic and ranks run bench.py --full too: every leg, as the
+#                         recorded passes did)
 #   trace:<cfg>[:<args>]  rocprofv3 --kernel-trace --stats of that bench run
 #   pmc:<cfg>:<counters>[:<args>]  one rocprofv3 --pmc pass (counters comma-separated; one block's
 #                         limits per pass, MI355X_MICROARCH.md)
@@ -38,27 +40,27 @@ for st in "$@"; do
         TAILN=6 run tests 1000 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
       fi ;;
     bench)
-      run "bench_$a1" 400 python bench.py --config "$a1" ${a2//,/ }
+      run "bench_$a1" 400 python bench.py --full --config "$a1" ${a2//,/ }
       grep '^{' "$O/bench_$a1.log" > "$O/bench_$a1.json" ;;
     trace)
       x=${a2:---steps,20,--warmup,3,--cpu-sample,0}
       run "trace_$a1" 400 rocprofv3 --kernel-trace --stats -d "$O/prof_$a1" -o "$a1" --output-format csv -- \
-        python3 bench.py --config "$a1" ${x//,/ } ;;
+        python3 bench.py --full --config "$a1" ${x//,/ } ;;
     pmc)
       x=${a3:---steps,5,--warmup,1,--cpu-sample,0}
       nm=$(echo "$a2" | tr ',' '_' | cut -c1-40)
       run "pmc_${a1}_$nm" 120 rocprofv3 --pmc ${a2//,/ } -d "$O/pmc_$a1" -o "pmc_$nm" --output-format csv -- \
-        python3 bench.py --config "$a1" ${x//,/ } ;;
+        python3 bench.py --full --config "$a1" ${x//,/ } ;;
     traffic)
       x=${a3:---steps,20,--warmup,3,--cpu-sample,0,--replicas,20}
       for k in FETCH_SIZE WRITE_SIZE; do
         run "traffic_${a1}_$k" 120 rocprofv3 --pmc $k -d "$O/traffic_$a1" -o "$k" --output-format csv -- \
-          python3 bench.py --config "$a1" ${x//,/ }
+          python3 bench.py --full --config "$a1" ${x//,/ }
       done
       run "traffic_${a1}_summary" 60 python3 scripts/pmc_summary.py --dir "$O/traffic_$a1" --kernel "$a2" \
         --out "$O/pmc_traffic_$a1.json" --bench-log "$O/traffic_${a1}_WRITE_SIZE.log" ;;  # copy into perf/ (bench.py reads it there) after the call
     ranks)
-      KPE_DIST_BACKEND=gloo run "ranks_$a1" 400 python bench.py --gpus "$a1" ${a2//,/ }
+      KPE_DIST_BACKEND=gloo run "ranks_$a1" 400 python bench.py --full --gpus "$a1" ${a2//,/ }
       grep '^{' "$O/ranks_$a1.log" > "$O/ranks_$a1.json" ;;
     *) echo "unknown step $st"; exit 2 ;;
   esac
