@@ -216,6 +216,43 @@ kpe_status kpe_unpack_verdicts(const uint32_t* packed, uint64_t cells, uint8_t* 
 kpe_status kpe_evaluate_sharded(kpe_device* const* devs, kpe_corpus* const* shards, int nshards,
                                 const kpe_program* prog, uint8_t* verdicts, kpe_counts* counts);
 
+/* ---- sparse result fetch -------------------------------------------------- */
+/* The cells a consumer needs, selected on the device, instead of kpe_fetch's whole N x R matrix
+ * and a host walk over it. After kpe_evaluate / kpe_evaluate_async of prog on the corpus (waits for
+ * it; KPE_E_STATE without one), like kpe_pack_verdicts.
+ *   sel : R bytes; cell (row, r) with verdict v is selected iff (sel[r] >> v) & 1.
+ * Writes the first min(total, cap) selected cells in ascending cell index (row * R + r) into
+ * cells[] (and their verdict codes into verdicts_out[] when not NULL); memory past that is not
+ * written. cells == NULL with cap == 0 counts only. Returns the total number of selected cells
+ * (call again with a larger buffer when it exceeds cap), or -kpe_status. cells[] is the list
+ * kpe_pattern_traces takes: KPE_SEL(KPE_FAIL) on the pattern rules' columns gives the cells whose
+ * failing paths the report needs (validate_resource.go:316-454). KPE_SEL_RESPONSES selects the cells
+ * that carry a RuleResponse (every code but KPE_NA), i.e. the cells EngineResponseToReportResults
+ * (pkg/utils/report/results.go:89-135) turns into report results, plus KPE_UNDECIDED cells. */
+#define KPE_SEL(v) (1u << (v))
+#define KPE_SEL_RESPONSES 0xFEu
+int64_t kpe_select_cells(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint8_t* sel,
+                         uint64_t* cells, uint8_t* verdicts_out, uint64_t cap);
+
+/* The `summary` block of each resource's report: CalculateSummary (pkg/utils/report/results.go:39-55)
+ * over the results EngineResponseToReportResults gives (:89-135; SetResponses -> SetResults ->
+ * CalculateSummary, :182-196; the CLI per policy, cmd/cli/kubectl-kyverno/report/report.go:93,104).
+ * Per row: KPE_PASS counts as pass, KPE_FAIL as fail, or as warn when the rule's policy is unscored
+ * (policies.kyverno.io/scored: "false", results.go:131-133), KPE_WARN as warn, KPE_ERROR as error,
+ * KPE_SKIP as skip; KPE_NA is not counted. `undecided` (not part of the reference's summary) counts
+ * the row's KPE_UNDECIDED cells: non-zero, the row needs the reference engine (kpe_counts.undecided
+ * by row). KPE_E_LIMIT for more than 65535 rules (16-bit counters). */
+typedef struct kpe_row_summary {
+  uint16_t pass, fail, warn, error, skip, undecided;
+} kpe_row_summary;
+/* Rows [row0, row0 + nrows) of the last evaluation of prog on the corpus, counted on the device
+ * (12 bytes per row come back instead of R); KPE_E_INVALID when row0 + nrows > N. */
+kpe_status kpe_fetch_row_summaries(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, uint64_t row0,
+                                   uint64_t nrows, kpe_row_summary* out);
+/* The same fold over nrows x R verdict bytes the caller holds. Host only; no device call. */
+kpe_status kpe_row_summaries_host(const kpe_program* prog, const uint8_t* verdicts, uint64_t nrows,
+                                  kpe_row_summary* out);
+
 /* PSA check id k (bit k of a check mask), e.g. "capabilities_restricted". */
 const char* kpe_pss_check_id(int k);
 int kpe_pss_num_checks(void);

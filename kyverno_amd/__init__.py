@@ -8,6 +8,9 @@ evaluation without a working gfx950 device raises KpeError.
 """
 from ._lib import KpeError, lib_path, load  # noqa: F401
 from .engine import (  # noqa: F401
+    SEL,
+    SEL_RESPONSES,
+    SUMMARY_FIELDS,
     SYNTH_C3,
     SYNTH_EDGE,
     SYNTH_FANOUT,
@@ -27,6 +30,7 @@ from .engine import (  # noqa: F401
     RuleStatus,
     cli_summary,
     report_results,
+    row_summaries,
     synth_ns_labels,
     synth_resources,
 )
@@ -45,6 +49,7 @@ __all__ = [
     "RuleStatus",
     "report_results",
     "cli_summary",
+    "row_summaries",
     "synth_ns_labels",
     "synth_resources",
     "load",

@@ -83,6 +83,12 @@ def load():
     L.kpe_packed_words.restype = ctypes.c_uint64
     L.kpe_pack_verdicts.argtypes = [vp, vp, vp, vp, ctypes.c_uint64]
     L.kpe_unpack_verdicts.argtypes = [vp, ctypes.c_uint64, vp]
+    L.kpe_select_cells.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_uint64]
+    L.kpe_select_cells.restype = i64
+    L.kpe_fetch_row_summaries.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp]
+    L.kpe_fetch_row_summaries.restype = ctypes.c_int
+    L.kpe_row_summaries_host.argtypes = [vp, vp, ctypes.c_uint64, vp]
+    L.kpe_row_summaries_host.restype = ctypes.c_int
     L.kpe_evaluate_sharded.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), i32, vp, vp, ctypes.POINTER(Counts)]
     L.kpe_fetch.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(Counts)]
     L.kpe_pss_check_id.argtypes = [i32]

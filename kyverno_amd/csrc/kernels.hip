@@ -1739,4 +1739,327 @@ extern "C" hipError_t kpe_launch_count(const uint8_t* verdicts, int64_t n, uint3
   }
   return hipSuccess;
 }
+
+// ---------------------------------------------------------------------------
+// Sparse result fetch (kpe_select_cells, kpe_fetch_row_summaries): reductions of the verdict
+// matrix read as a flat array of N x R bytes, 16 cells per lane with one 16-byte load (the matrix
+// is a hipMalloc allocation, so a multiple of 16 from its base is aligned); a block tile is
+// 256 x 16 = 4096 cells. A lane's tail is bounded by count: no byte past the range is read.
+// Per-rule byte tables (the selection masks, the unscored flags) are staged in LDS up to
+// kSelLdsRules rules and read from global memory past that.
+constexpr uint32_t kSelTile = 4096;
+constexpr uint32_t kSelLdsRules = 16384;
+constexpr uint32_t kSelGrid = 2048;   // persistent blocks of the selection kernels (8 per CU: every wave slot)
+constexpr uint32_t kSumRows = 1024;   // rows a block of the summary kernel counts at a time (24 KiB of LDS)
+constexpr uint32_t kSumGrid = 1536;   // persistent blocks of the summary kernel (6 per CU: what its LDS allows)
+
+namespace {
+struct Cells16 {
+  uint32_t w[4];
+  __device__ __forceinline__ uint32_t at(uint32_t k) const {  // k: compile-time after unrolling
+    return (w[k >> 2] >> (8u * (k & 3u))) & 0xFFu;
+  }
+  __device__ __forceinline__ uint32_t at_dyn(uint32_t k) const {
+    const uint64_t lo = (uint64_t)w[0] | ((uint64_t)w[1] << 32), hi = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
+    return (uint32_t)((k < 8u ? lo >> (8u * k) : hi >> (8u * (k - 8u))) & 0xFFu);
+  }
+};
+// cells [f, f + cnt) of the matrix, cnt <= 16, f a multiple of 16
+__device__ __forceinline__ Cells16 load_cells(const uint8_t* __restrict__ v, uint64_t f, uint32_t cnt) {
+  Cells16 c;
+  if (cnt == 16u) {
+    const uint4 q = *reinterpret_cast<const uint4*>(v + f);
+    c.w[0] = q.x, c.w[1] = q.y, c.w[2] = q.z, c.w[3] = q.w;
+  } else {
+    c.w[0] = c.w[1] = c.w[2] = c.w[3] = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < 15u; ++k)
+      if (k < cnt) c.w[k >> 2] |= (uint32_t)v[f + k] << (8u * (k & 3u));
+  }
+  return c;
+}
+__device__ __forceinline__ uint32_t flat_col(uint64_t f, uint32_t R) {
+  return (f >> 32) == 0 ? (uint32_t)f % R : (uint32_t)(f % R);
+}
+// column k <= 4 cells after column col
+__device__ __forceinline__ uint32_t col_add(uint32_t col, uint32_t k, uint32_t R) {
+  col += k;
+  return col < R ? col : (R >= k ? col - R : col % R);
+}
+// bit k: cell f + k is selected (the cell's verdict v has bit v of its rule's mask set). skip_na
+// (uniform: no rule selects KPE_NA): a word of four NA cells is passed over without its table
+// reads; most cells of a wide matrix are NA. Cells past cnt are zero and never selected.
+__device__ __forceinline__ uint32_t sel_hits(const Cells16& c, uint32_t cnt, uint32_t col, uint32_t R,
+                                             const uint8_t* tbl, bool skip_na) {
+  uint32_t m = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < 4u; ++w) {
+    if (skip_na && c.w[w] == 0u) {
+      col = col_add(col, 4u, R);
+      continue;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+      const uint32_t k = 4u * w + j;
+      const uint32_t v = c.at(k);
+      const uint32_t s = tbl[col];
+      if (k < cnt && v < 8u && ((s >> v) & 1u)) m |= 1u << k;
+      col = col + 1u == R ? 0u : col + 1u;
+    }
+  }
+  return m;
+}
+// the block's per-rule byte table: staged in LDS (uniform branch), or the global one
+template <bool LDS>
+__device__ __forceinline__ const uint8_t* stage_table(const uint8_t* __restrict__ g, uint32_t R, uint8_t* lds) {
+  if (!LDS) return g;
+  for (uint32_t i = threadIdx.x; i < R; i += 256u) lds[i] = g[i];
+  __syncthreads();
+  return lds;
+}
+}  // namespace
+
+// Pass 1: selected cells per tile (popcount of each lane's 16-bit hit mask, block sum).
+template <bool LDS>
+__global__ void __launch_bounds__(256) kpe_select_count_kernel(const uint8_t* __restrict__ v, uint64_t cells, uint32_t R,
+                                                               const uint8_t* __restrict__ sel, uint32_t skip_na,
+                                                               uint32_t* __restrict__ tile_counts, uint64_t ntiles) {
+  extern __shared__ uint8_t s_sel_tbl[];
+  __shared__ uint32_t s_w[2][4];  // by tile parity: one barrier per tile
+  const uint32_t t = threadIdx.x;
+  const uint8_t* tbl = stage_table<LDS>(sel, R, s_sel_tbl);
+  uint32_t par = 0;
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, par ^= 1u) {
+    const uint64_t f = tile * kSelTile + t * 16u;
+    const uint32_t cnt = f >= cells ? 0u : (cells - f < 16u ? (uint32_t)(cells - f) : 16u);
+    uint32_t hits = 0;
+    if (cnt) hits = __popc(sel_hits(load_cells(v, f, cnt), cnt, flat_col(f, R), R, tbl, skip_na != 0u));
+    const uint32_t inc = wave_incl_scan(hits);
+    if ((t & 63u) == 63u) s_w[par][t >> 6] = inc;
+    __syncthreads();
+    if (t == 0) tile_counts[tile] = s_w[par][0] + s_w[par][1] + s_w[par][2] + s_w[par][3];
+  }
+}
+
+// Pass 2: exclusive 64-bit scan of the tile counts, offs[ntiles] = the total. One block, 4096
+// tiles per round (16 per thread, four 16-byte loads: tile_counts is 16-byte aligned and padded to
+// a multiple of four entries).
+__global__ void __launch_bounds__(256) kpe_select_scan_kernel(const uint32_t* __restrict__ tile_counts,
+                                                              uint64_t* __restrict__ offs, uint64_t ntiles) {
+  __shared__ uint32_t s_w[4];
+  const uint32_t t = threadIdx.x;
+  uint64_t carry = 0;
+  for (uint64_t base = 0; base < ntiles; base += 4096u) {
+    const uint64_t i0 = base + t * 16u;
+    uint32_t c[16], sum = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q) {
+      uint4 x = make_uint4(0u, 0u, 0u, 0u);
+      if (i0 + 4u * q < ntiles) x = *reinterpret_cast<const uint4*>(tile_counts + i0 + 4u * q);
+      c[4u * q] = x.x, c[4u * q + 1u] = x.y, c[4u * q + 2u] = x.z, c[4u * q + 3u] = x.w;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; ++k) {
+      if (i0 + k >= ntiles) c[k] = 0u;  // the padding
+      sum += c[k];
+    }
+    const uint32_t inc = wave_incl_scan(sum);  // <= 256 x 16 x 4096: 32 bits hold a round
+    if ((t & 63u) == 63u) s_w[t >> 6] = inc;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 4u; ++w) {
+      if (w < (t >> 6)) before += s_w[w];
+      all += s_w[w];
+    }
+    uint64_t o = carry + before + (inc - sum);
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; ++k) {
+      if (i0 + k < ntiles) offs[i0 + k] = o;
+      o += c[k];
+    }
+    carry += all;
+    __syncthreads();
+  }
+  if (t == 0) offs[ntiles] = carry;
+}
+
+// Pass 3: the hit masks again; a lane's first output slot is its tile's offset + the waves before
+// it (LDS) + the lanes before it (DPP scan). Only slots below cap are written. Tiles without a
+// selected cell, and tiles that start at or past cap, are not read.
+template <bool LDS>
+__global__ void __launch_bounds__(256) kpe_select_scatter_kernel(const uint8_t* __restrict__ v, uint64_t cells, uint32_t R,
+                                                                 const uint8_t* __restrict__ sel, uint32_t skip_na,
+                                                                 const uint64_t* __restrict__ offs, uint64_t ntiles,
+                                                                 uint64_t cap, uint64_t* __restrict__ out_cells,
+                                                                 uint8_t* __restrict__ out_v) {
+  extern __shared__ uint8_t s_sel_tbl[];
+  __shared__ uint32_t s_w[4];
+  const uint32_t t = threadIdx.x;
+  const uint8_t* tbl = stage_table<LDS>(sel, R, s_sel_tbl);
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const uint64_t o0 = offs[tile], o1 = offs[tile + 1];  // uniform
+    if (o0 == o1 || o0 >= cap) continue;
+    const uint64_t f = tile * kSelTile + t * 16u;
+    const uint32_t cnt = f >= cells ? 0u : (cells - f < 16u ? (uint32_t)(cells - f) : 16u);
+    Cells16 c;
+    uint32_t m = 0;
+    if (cnt) {
+      c = load_cells(v, f, cnt);
+      m = sel_hits(c, cnt, flat_col(f, R), R, tbl, skip_na != 0u);
+    }
+    const uint32_t hits = __popc(m);
+    const uint32_t inc = wave_incl_scan(hits);
+    if ((t & 63u) == 63u) s_w[t >> 6] = inc;
+    __syncthreads();
+    uint32_t before = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 3u; ++w)
+      if (w < (t >> 6)) before += s_w[w];
+    uint64_t o = o0 + before + (inc - hits);
+    while (m) {
+      const uint32_t k = (uint32_t)__builtin_ctz(m);
+      m &= m - 1u;
+      if (o < cap) {
+        out_cells[o] = f + k;
+        if (out_v) out_v[o] = (uint8_t)c.at_dyn(k);
+      }
+      ++o;
+    }
+    __syncthreads();
+  }
+}
+
+// CalculateSummary per resource (pkg/utils/report/results.go:39-55 over :89-135): rows
+// [row0, row0 + nrows), 6 uint16 counters per row (pass, fail, warn, error, skip, undecided) as 3
+// words. A block takes groups of rows_per_group whole rows (<= kSumRows, about one tile of bytes),
+// reads their contiguous bytes with the aligned 16-byte loads (cells before the group's first byte
+// are skipped by index) and counts each lane's cells of one row in a register (5 bits per counter)
+// before adding them to the row's LDS counters; each row is written once. With R >= 16 a lane's 16
+// cells lie in at most two rows: two registers, no branch per cell, and words of four KPE_NA cells
+// (most of a wide matrix) are passed over. unscored[r] != 0: a FAIL of rule r counts as warn
+// (results.go:131-133).
+template <bool LDS>
+__global__ void __launch_bounds__(256) kpe_row_summary_kernel(const uint8_t* __restrict__ v, uint32_t R, uint64_t row0,
+                                                              uint64_t nrows, uint32_t rows_per_group,
+                                                              const uint8_t* __restrict__ unscored,
+                                                              uint32_t* __restrict__ out) {
+  extern __shared__ uint8_t s_sel_tbl[];
+  __shared__ uint32_t s_cnt[kSumRows * 6u];
+  const uint32_t t = threadIdx.x;
+  const uint8_t* tbl = stage_table<LDS>(unscored, R, s_sel_tbl);
+  const uint64_t ngroups = (nrows + rows_per_group - 1u) / rows_per_group;
+  // a lane's counts of one row (5 bits per counter, at most 16 cells) into the row's LDS counters
+  auto flush = [&](uint32_t acc, uint32_t lrow) {
+    while (acc) {
+      const uint32_t s = (uint32_t)__builtin_ctz(acc) / 5u;
+      atomicAdd(&s_cnt[lrow * 6u + s], (acc >> (5u * s)) & 31u);
+      acc &= ~(31u << (5u * s));
+    }
+  };
+  // the counter increment of verdict code x of rule col (0: not counted). Code -> counter + 1:
+  // PASS, FAIL (or warn), WARN, ERROR, SKIP, -, UNDECIDED
+  auto cell_inc = [&](uint32_t x, uint32_t col) -> uint32_t {
+    const uint32_t lut = 0x60543210u + (tbl[col] ? 0x100u : 0u);
+    const uint32_t slot = x < 8u ? (lut >> (4u * x)) & 15u : 0u;
+    return (1u << (5u * slot)) >> 5;
+  };
+  for (uint64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const uint64_t r0 = g * rows_per_group;  // relative to row0
+    const uint32_t rn = nrows - r0 < rows_per_group ? (uint32_t)(nrows - r0) : rows_per_group;
+    for (uint32_t i = t; i < rn * 6u; i += 256u) s_cnt[i] = 0u;
+    __syncthreads();
+    const uint64_t g0 = (row0 + r0) * R, g1 = g0 + (uint64_t)rn * R;  // the group's bytes: < 2^32 of them
+    for (uint64_t c0 = (g0 & ~(uint64_t)15u) + t * 16u; c0 < g1; c0 += kSelTile) {
+      const uint32_t cnt = g1 - c0 < 16u ? (uint32_t)(g1 - c0) : 16u;
+      const uint32_t k0 = c0 < g0 ? (uint32_t)(g0 - c0) : 0u;  // c0 may start up to 15 cells before the group
+      if (k0 >= cnt) continue;
+      const Cells16 c = load_cells(v, c0, cnt);
+      const uint32_t rel = (uint32_t)(c0 + k0 - g0);
+      uint32_t lrow = rel / R, col = rel - lrow * R;
+      if (R >= 16u) {  // uniform: cell k is in row lrow, or in lrow + 1 once its column wraps
+        uint32_t acc0 = 0, acc1 = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 4u; ++w) {
+          if (c.w[w] == 0u) continue;
+#pragma unroll
+          for (uint32_t j = 0; j < 4u; ++j) {
+            const uint32_t k = 4u * w + j;
+            const uint32_t ck = col + (k >= k0 ? k - k0 : 0u);  // < 2 R
+            const bool next = ck >= R;
+            const uint32_t inc = (k >= k0 && k < cnt) ? cell_inc(c.at(k), next ? ck - R : ck) : 0u;
+            acc0 += next ? 0u : inc;
+            acc1 += next ? inc : 0u;
+          }
+        }
+        flush(acc0, lrow);
+        flush(acc1, lrow + 1u);  // non-zero only when a counted cell lies in that row
+      } else {
+        uint32_t acc = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; ++k) {
+          if (k >= k0 && k < cnt) {
+            acc += cell_inc(c.at(k), col);
+            if (++col == R) {
+              flush(acc, lrow);
+              acc = 0, col = 0, ++lrow;
+            }
+          }
+        }
+        flush(acc, lrow);
+      }
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < rn * 3u; i += 256u) out[r0 * 3u + i] = s_cnt[2u * i] | (s_cnt[2u * i + 1u] << 16);
+    __syncthreads();
+  }
+}
+
+// tile_counts: ntiles words, tile_offs: ntiles + 1 offsets (the last one is the total)
+// na_selected: some rule's mask selects KPE_NA
+extern "C" hipError_t kpe_launch_select_count(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* sel,
+                                              int na_selected, uint32_t* tile_counts, uint64_t* tile_offs,
+                                              hipStream_t s) {
+  if (!cells || !R) return hipSuccess;
+  const uint64_t ntiles = (cells + kSelTile - 1u) / kSelTile;
+  const dim3 grid((unsigned)std::min<uint64_t>(ntiles, kSelGrid));
+  const uint32_t skip_na = na_selected ? 0u : 1u;
+  if (R <= kSelLdsRules)
+    hipLaunchKernelGGL(kpe_select_count_kernel<true>, grid, dim3(256), (size_t)R, s, v, cells, R, sel, skip_na,
+                       tile_counts, ntiles);
+  else
+    hipLaunchKernelGGL(kpe_select_count_kernel<false>, grid, dim3(256), 0, s, v, cells, R, sel, skip_na, tile_counts,
+                       ntiles);
+  hipLaunchKernelGGL(kpe_select_scan_kernel, dim3(1), dim3(256), 0, s, tile_counts, tile_offs, ntiles);
+  return hipGetLastError();
+}
+// out_cells / out_v (may be NULL): at least min(total, cap) entries
+extern "C" hipError_t kpe_launch_select_scatter(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* sel,
+                                                int na_selected, const uint64_t* tile_offs, uint64_t cap,
+                                                uint64_t* out_cells, uint8_t* out_v, hipStream_t s) {
+  if (!cells || !R || !cap) return hipSuccess;
+  const uint64_t ntiles = (cells + kSelTile - 1u) / kSelTile;
+  const dim3 grid((unsigned)std::min<uint64_t>(ntiles, kSelGrid));
+  const uint32_t skip_na = na_selected ? 0u : 1u;
+  if (R <= kSelLdsRules)
+    hipLaunchKernelGGL(kpe_select_scatter_kernel<true>, grid, dim3(256), (size_t)R, s, v, cells, R, sel, skip_na,
+                       tile_offs, ntiles, cap, out_cells, out_v);
+  else
+    hipLaunchKernelGGL(kpe_select_scatter_kernel<false>, grid, dim3(256), 0, s, v, cells, R, sel, skip_na, tile_offs,
+                       ntiles, cap, out_cells, out_v);
+  return hipGetLastError();
+}
+// out: 3 words per row of [row0, row0 + nrows); R <= 65535 (the counters are 16 bits wide)
+extern "C" hipError_t kpe_launch_row_summary(const uint8_t* v, uint32_t R, uint64_t row0, uint64_t nrows,
+                                             const uint8_t* unscored, uint32_t* out, hipStream_t s) {
+  if (!nrows || !R) return hipSuccess;
+  const uint32_t rpg = std::max<uint32_t>(1u, std::min<uint32_t>(kSumRows, kSelTile / R));
+  const uint64_t ngroups = (nrows + rpg - 1u) / rpg;
+  const dim3 grid((unsigned)std::min<uint64_t>(ngroups, kSumGrid));
+  if (R <= kSelLdsRules)
+    hipLaunchKernelGGL(kpe_row_summary_kernel<true>, grid, dim3(256), (size_t)R, s, v, R, row0, nrows, rpg, unscored, out);
+  else
+    hipLaunchKernelGGL(kpe_row_summary_kernel<false>, grid, dim3(256), 0, s, v, R, row0, nrows, rpg, unscored, out);
+  return hipGetLastError();
+}
 #endif  // !KPE_VM_ONLY

@@ -54,6 +54,14 @@ extern "C" hipError_t kpe_launch_leaf_table(const PatArgs* dargs, const uint32_t
                                             uint64_t nscal, hipStream_t s);
 extern "C" hipError_t kpe_launch_count(const uint8_t* verdicts, int64_t n, uint32_t R, unsigned long long* out,
                                        hipStream_t s);
+extern "C" hipError_t kpe_launch_select_count(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* sel,
+                                              int na_selected, uint32_t* tile_counts, uint64_t* tile_offs,
+                                              hipStream_t s);
+extern "C" hipError_t kpe_launch_select_scatter(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* sel,
+                                                int na_selected, const uint64_t* tile_offs, uint64_t cap,
+                                                uint64_t* out_cells, uint8_t* out_v, hipStream_t s);
+extern "C" hipError_t kpe_launch_row_summary(const uint8_t* v, uint32_t R, uint64_t row0, uint64_t nrows,
+                                             const uint8_t* unscored, uint32_t* out, hipStream_t s);
 
 namespace {
 thread_local std::string g_err;
@@ -2119,6 +2127,119 @@ kpe_status kpe_pack_verdicts(kpe_device* dev, const kpe_program* prog, const kpe
 kpe_status kpe_unpack_verdicts(const uint32_t* packed, uint64_t cells, uint8_t* out) {
   if ((!packed || !out) && cells) return fail(KPE_E_INVALID, "null argument");
   for (uint64_t i = 0; i < cells; ++i) out[i] = (uint8_t)((packed[i / 10u] >> (3u * (uint32_t)(i % 10u))) & 7u);
+  return KPE_OK;
+}
+
+// ---- sparse result fetch: cell selection and row summaries ------------------------------------
+static kpe_status select_impl(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint8_t* sel,
+                              uint64_t* cells_out, uint8_t* verdicts_out, uint64_t cap, uint64_t* total_out) {
+  *total_out = 0;
+  if (!dev || !prog || !c || !sel) return fail(KPE_E_INVALID, "null argument");
+  if (cap && !cells_out) return fail(KPE_E_INVALID, "cap > 0 without a cells buffer");
+  const size_t R = prog->p->rules.size();
+  const uint64_t cells = (uint64_t)c->c->n * R;
+  if (!cells) return KPE_OK;
+  if (!c->d) return fail(KPE_E_STATE, "corpus not uploaded");
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  auto& B = c->d->bind;
+  if (B.prog != prog->p.get()) return fail(KPE_E_STATE, "no evaluation of this program on this corpus");
+  if (c->d->ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  hipStream_t s = B.last ? B.last : dev->stream;
+  // scratch of this call (freed on every return path): tile offsets, tile counts, the masks
+  const uint64_t ntiles = (cells + 4095u) / 4096u;
+  const size_t off_bytes = (size_t)((ntiles + 2) & ~(uint64_t)1) * 8;  // + the total, kept 16-byte aligned
+  const size_t cnt_bytes = (size_t)((ntiles + 3) & ~(uint64_t)3) * 4;  // read four at a time
+  DevBuf scratch, dcells, dverd;
+  HIPCHK(scratch.ensure(off_bytes + cnt_bytes + R));
+  uint64_t* d_off = scratch.as<uint64_t>();
+  uint32_t* d_cnt = reinterpret_cast<uint32_t*>(scratch.as<uint8_t>() + off_bytes);
+  uint8_t* d_sel = scratch.as<uint8_t>() + off_bytes + cnt_bytes;
+  HIPCHK(hipMemcpyAsync(d_sel, sel, R, hipMemcpyHostToDevice, s));
+  int na_sel = 0;  // most cells of a wide matrix are KPE_NA: the kernels pass over them unless a mask selects them
+  for (size_t r = 0; r < R; ++r) na_sel |= sel[r] & 1;
+  HIPCHK(kpe_launch_select_count(B.verdicts.as<uint8_t>(), cells, (uint32_t)R, d_sel, na_sel, d_cnt, d_off, s));
+  uint64_t total = 0;
+  HIPCHK(hipMemcpyAsync(&total, d_off + ntiles, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *total_out = total;
+  const uint64_t m = std::min(total, cap);
+  if (!m) return KPE_OK;
+  // staging sized by what is written, not by cap
+  HIPCHK(dcells.ensure((size_t)m * 8));
+  if (verdicts_out) HIPCHK(dverd.ensure((size_t)m));
+  HIPCHK(kpe_launch_select_scatter(B.verdicts.as<uint8_t>(), cells, (uint32_t)R, d_sel, na_sel, d_off, m,
+                                   dcells.as<uint64_t>(), verdicts_out ? dverd.as<uint8_t>() : nullptr, s));
+  HIPCHK(hipMemcpyAsync(cells_out, dcells.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+  if (verdicts_out) HIPCHK(hipMemcpyAsync(verdicts_out, dverd.p, (size_t)m, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return KPE_OK;
+}
+
+int64_t kpe_select_cells(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint8_t* sel,
+                         uint64_t* cells, uint8_t* verdicts_out, uint64_t cap) {
+  uint64_t total = 0;
+  const kpe_status st = select_impl(dev, prog, c, sel, cells, verdicts_out, cap, &total);
+  return st ? -(int64_t)st : (int64_t)total;
+}
+
+// the counter of a verdict cell (results.go:39-55; an unscored fail is a warn, :131-133)
+static inline void summary_add(kpe_row_summary& o, uint8_t v, bool scored) {
+  switch (v) {
+    case KPE_PASS: ++o.pass; break;
+    case KPE_FAIL: ++(scored ? o.fail : o.warn); break;
+    case KPE_WARN: ++o.warn; break;
+    case KPE_ERROR: ++o.error; break;
+    case KPE_SKIP: ++o.skip; break;
+    case KPE_UNDECIDED: ++o.undecided; break;
+    default: break;  // KPE_NA: no RuleResponse
+  }
+}
+
+kpe_status kpe_row_summaries_host(const kpe_program* prog, const uint8_t* verdicts, uint64_t nrows,
+                                  kpe_row_summary* out) {
+  if (!prog || (nrows && (!verdicts || !out))) return fail(KPE_E_INVALID, "null argument");
+  const kpe::Program& P = *prog->p;
+  const size_t R = P.rules.size();
+  if (R > 65535) return fail(KPE_E_LIMIT, "row summaries count at most 65535 rules");
+  for (uint64_t i = 0; i < nrows; ++i) {
+    kpe_row_summary o{};
+    for (size_t r = 0; r < R; ++r) summary_add(o, verdicts[i * R + r], P.reports[r].scored);
+    out[i] = o;
+  }
+  return KPE_OK;
+}
+
+kpe_status kpe_fetch_row_summaries(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, uint64_t row0,
+                                   uint64_t nrows, kpe_row_summary* out) {
+  if (!dev || !prog || !c || (nrows && !out)) return fail(KPE_E_INVALID, "null argument");
+  const kpe::Program& P = *prog->p;
+  const size_t R = P.rules.size();
+  if (R > 65535) return fail(KPE_E_LIMIT, "row summaries count at most 65535 rules");
+  if (row0 > (uint64_t)c->c->n || nrows > (uint64_t)c->c->n - row0) return fail(KPE_E_INVALID, "rows past the corpus");
+  if (!nrows) return KPE_OK;
+  if (!R) {
+    memset(out, 0, nrows * sizeof(kpe_row_summary));
+    return KPE_OK;
+  }
+  if (!c->d) return fail(KPE_E_STATE, "corpus not uploaded");
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  auto& B = c->d->bind;
+  if (B.prog != prog->p.get()) return fail(KPE_E_STATE, "no evaluation of this program on this corpus");
+  if (c->d->ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  hipStream_t s = B.last ? B.last : dev->stream;
+  std::vector<uint8_t> unscored(R);
+  for (size_t r = 0; r < R; ++r) unscored[r] = P.reports[r].scored ? 0 : 1;
+  static_assert(sizeof(kpe_row_summary) == 12, "3 words per row");
+  const size_t out_bytes = (size_t)nrows * sizeof(kpe_row_summary);
+  DevBuf scratch;  // this call's: the rows' summaries, then the unscored flags
+  HIPCHK(scratch.ensure(out_bytes + R));
+  uint8_t* d_uns = scratch.as<uint8_t>() + out_bytes;
+  HIPCHK(hipMemcpyAsync(d_uns, unscored.data(), R, hipMemcpyHostToDevice, s));
+  HIPCHK(kpe_launch_row_summary(B.verdicts.as<uint8_t>(), (uint32_t)R, row0, nrows, d_uns, scratch.as<uint32_t>(), s));
+  HIPCHK(hipMemcpyAsync(out, scratch.p, out_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return KPE_OK;
 }
 

@@ -361,6 +361,44 @@ class Engine:
         """3-bit packing of the verdict matrix into device memory at dst_ptr (kpe_pack_verdicts)."""
         check(load().kpe_pack_verdicts(self.device.h, ps.h, corpus.h, ctypes.c_void_p(dst_ptr), words))
 
+    # ---- sparse result fetch (device-side selection and row summaries) ----
+    def select_cells(self, ps: PolicySet, corpus: Corpus, sel, cap: Optional[int] = None, with_verdicts=True):
+        """The selected cells of the last evaluation of ps on corpus (kpe_select_cells), in
+        ascending cell index: (cells uint64 = row * R + column, their verdicts uint8, total).
+        sel: a mask of kpe_verdict bits (SEL(v), SEL_RESPONSES) for every rule, or one per rule.
+        cap: at most that many cells come back (total still counts all of them); None: a count
+        call, then a call of exactly that size. cells is the list pattern_traces takes."""
+        L = load()
+        R = ps.num_rules
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(sel, dtype=np.uint8), (R,)) if np.ndim(sel) == 0
+                                 else np.asarray(sel, dtype=np.uint8))
+        if s.shape != (R,):
+            raise ValueError("sel: one mask, or one per rule")
+        sbuf = s if R else np.zeros(1, dtype=np.uint8)
+
+        def call(cells, verd, n):
+            t = L.kpe_select_cells(self.device.h, ps.h, corpus.h, sbuf.ctypes.data, cells.ctypes.data if n else None,
+                                   verd.ctypes.data if (verd is not None and n) else None, n)
+            if t < 0:
+                check(-t)
+            return int(t)
+
+        n = call(None, None, 0) if cap is None else min(int(cap), corpus.n * R)  # never more than every cell
+        cells = np.zeros(n, dtype=np.uint64)
+        verd = np.zeros(n, dtype=np.uint8) if with_verdicts else None
+        total = call(cells, verd, n) if (n or cap is not None) else 0
+        k = min(total, n)
+        return cells[:k], (verd[:k] if with_verdicts else np.zeros(0, dtype=np.uint8)), total
+
+    def row_summaries(self, ps: PolicySet, corpus: Corpus, row0: int = 0, nrows: Optional[int] = None) -> np.ndarray:
+        """The report `summary` counters of rows [row0, row0 + nrows) of the last evaluation of ps
+        on corpus, counted on the device (kpe_fetch_row_summaries): (nrows, 6) uint16, columns
+        SUMMARY_FIELDS (pass, fail, warn, error, skip, undecided)."""
+        n = corpus.n - row0 if nrows is None else nrows
+        out = np.zeros((max(n, 0), 6), dtype=np.uint16)
+        check(load().kpe_fetch_row_summaries(self.device.h, ps.h, corpus.h, row0, n, out.ctypes.data if n > 0 else None))
+        return out
+
     def pattern_traces(self, ps: PolicySet, corpus: Corpus, cells) -> np.ndarray:
         """Failing-path records of pattern cells (kpe_pattern_traces) after an evaluation of ps on
         corpus: cells = flat indices row * R + column; returns (len(cells), KPE_TRACE_ROOTS,
@@ -498,6 +536,32 @@ def report_results(ps: PolicySet, verdict_row, cv_mask_row=None, resource=None, 
         if n < cap:
             return json.loads(buf.value.decode())
         cap = n + 1
+
+
+SEL_RESPONSES = 0xFE  # include/kpe.h KPE_SEL_RESPONSES: every verdict code but KPE_NA
+SUMMARY_FIELDS = ("pass", "fail", "warn", "error", "skip", "undecided")  # kpe_row_summary, in order
+
+
+def SEL(v: int) -> int:
+    """include/kpe.h KPE_SEL(v): the selection mask bit of verdict code v."""
+    return 1 << int(v)
+
+
+def row_summaries(ps: PolicySet, verdicts) -> np.ndarray:
+    """CalculateSummary (pkg/utils/report/results.go:39-55) of each row of an (n, R) verdict
+    matrix the caller holds, through kpe_row_summaries_host (no device call): (n, 6) uint16,
+    columns SUMMARY_FIELDS. An unscored policy's fails count as warn; `undecided` counts the
+    row's KPE_UNDECIDED cells."""
+    v = np.ascontiguousarray(verdicts, dtype=np.uint8)
+    R = ps.num_rules
+    if v.ndim == 1:
+        v = v.reshape(1, -1)
+    if v.ndim != 2 or v.shape[1] != R:
+        raise ValueError("verdicts: rows of one cell per rule")
+    out = np.zeros((v.shape[0], 6), dtype=np.uint16)
+    check(load().kpe_row_summaries_host(ps.h, v.ctypes.data if v.size else None, v.shape[0] if R else 0,
+                                        out.ctypes.data if v.shape[0] else None))
+    return out
 
 
 def cli_summary(ps: PolicySet, counts: List[dict], audit_warn: bool = False) -> Dict[str, int]:
