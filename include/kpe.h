@@ -151,6 +151,25 @@ kpe_status kpe_resource_hash(const char* resource_json, size_t len, char* out33)
  * flattener keeps with KPE_ROW_DECODE_ERROR) has no hash: its 32 bytes are '-' (never a hex
  * digest), so an incremental scan always re-evaluates it. */
 int64_t kpe_resource_hashes(const char* ndjson, size_t len, char* out, int64_t cap_rows);
+/* Namespace groups of the corpus (host only, no device call). A resource's group is the namespace
+ * the flattener recorded as its metadata.namespace, i.e. unstructured GetNamespace(), the value
+ * GetValidationFailureAction (pkg/engine/api/engineresponse.go:196-225) compares and the key of the
+ * CLI's NamespaceSelectorMap (cmd/cli/kubectl-kyverno/processor/policy_processor.go:63). It is not
+ * the match namespace: a `kind: Namespace` object groups under "" like every cluster-scoped
+ * resource, not under its own name. Group ids are dense in [0, G) and fixed for the corpus's
+ * lifetime (the ids of its namespace dictionary, which also holds the names of Namespace objects:
+ * a group may have no rows). The group "" always exists; a row without a namespace string (no
+ * metadata.namespace, or a row whose recorded id is outside the dictionary, such as KPE_NO_STR)
+ * belongs to it. kpe_corpus_flatten refuses a line that is not a JSON object, so no row lacks a
+ * recorded id today. */
+int64_t kpe_corpus_num_namespaces(const kpe_corpus* c);
+/* Name of group g (owned by the corpus; NULL when g is out of range). */
+const char* kpe_corpus_namespace(const kpe_corpus* c, int64_t g);
+/* out[i] = the group of row i, for each of the kpe_corpus_num_resources rows. */
+kpe_status kpe_corpus_row_namespaces(const kpe_corpus* c, uint32_t* out);
+/* out[g] = the rows of group g (G entries; their sum is N). The KPE_NA cells of a (group, rule)
+ * are these rows minus the six counters of kpe_ns_counts. */
+kpe_status kpe_corpus_namespace_rows(const kpe_corpus* c, uint64_t* out);
 /* Copy the columns to device memory (HBM). Evaluation requires this. */
 kpe_status kpe_corpus_upload(kpe_device* dev, kpe_corpus* c);
 /* The corpus's per-pod PSA summary, built on dev (waits for it; builds it first when no LEAN
@@ -253,6 +272,32 @@ kpe_status kpe_fetch_row_summaries(kpe_device* dev, const kpe_program* prog, con
 kpe_status kpe_row_summaries_host(const kpe_program* prog, const uint8_t* verdicts, uint64_t nrows,
                                   kpe_row_summary* out);
 
+/* ---- per-namespace rule counts ---------------------------------------------- */
+/* The verdict matrix reduced by namespace group on the device: per (group, rule) the cells of each
+ * raw verdict code. `fail` counts KPE_FAIL cells whether or not the policy is scored, `warn`
+ * KPE_WARN, `undecided` KPE_UNDECIDED; KPE_NA is not counted (kpe_corpus_namespace_rows gives it).
+ * The scored / audit fold is the consumer's (kpe_cli_summary_ns): the action depends on the group.
+ * It is the table per-namespace compliance views are built from, and what `kyverno apply
+ * --audit-warn` needs for policies with validationFailureActionOverrides
+ * (ResultCounts.addEngineResponse, cmd/cli/kubectl-kyverno/processor/result.go:53, asks
+ * response.GetValidationFailureAction(), a function of the policy, the resource's GetNamespace()
+ * and that namespace's labels, engineresponse.go:196-225), without copying the N x R matrix back. */
+typedef struct kpe_ns_counts {
+  uint32_t pass, fail, warn, error, skip, undecided;
+} kpe_ns_counts; /* 24 bytes */
+/* Groups [g0, g0 + ng) of the last evaluation of prog on the corpus: out[(g - g0) * R + r]. After
+ * kpe_evaluate / kpe_evaluate_async / kpe_evaluate_batch_async of prog on the corpus (waits for it;
+ * KPE_E_STATE without one), like kpe_fetch_row_summaries. KPE_E_INVALID when g0 + ng > G or for a
+ * null argument (checked before any device call); ng == 0 writes nothing; memory past ng * R
+ * entries is not written. KPE_E_LIMIT for 2^32 rows or more (32-bit counters). The first call on an
+ * uploaded corpus builds the corpus's rows-by-namespace index and keeps it on the device. */
+kpe_status kpe_fetch_namespace_counts(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, uint64_t g0,
+                                      uint64_t ng, kpe_ns_counts* out);
+/* The same fold over N x R verdict bytes the caller holds (N = the corpus's rows). Host only; no
+ * device call. */
+kpe_status kpe_namespace_counts_host(const kpe_program* prog, const kpe_corpus* c, const uint8_t* verdicts,
+                                     uint64_t g0, uint64_t ng, kpe_ns_counts* out);
+
 /* PSA check id k (bit k of a check mask), e.g. "capabilities_restricted". */
 const char* kpe_pss_check_id(int k);
 int kpe_pss_num_checks(void);
@@ -282,6 +327,23 @@ typedef struct kpe_cli_totals {
   uint64_t pass, fail, warn, error, skip;
 } kpe_cli_totals;
 kpe_status kpe_cli_summary(const kpe_program* prog, const kpe_counts* counts, int audit_warn, kpe_cli_totals* out);
+/* The same summary line from the per-namespace table (counts: G x R entries, every group of the
+ * corpus), with the action resolved per group: for policies with validationFailureActionOverrides
+ * it restates GetValidationFailureAction (engineresponse.go:196-225). Overrides are taken in
+ * order; one whose action is not audit / enforce / Audit / Enforce is skipped (api/kyverno/v1/
+ * spec_types.go:39-41). With `namespaces` absent (nil) the override applies when CheckSelector
+ * (pkg/utils/match/labels.go:10-24) holds for namespaceSelector over the group's namespace labels:
+ * a nil selector is false, a selector that does not build is false, wildcards in matchLabels keys
+ * and values are expanded against the labels first (wildcards.ReplaceInSelector). Otherwise it
+ * applies when an entry of `namespaces` matches the group's name (go-wildcard) and the selector is
+ * nil or holds; `namespaces: []` (present, empty) never applies. The first applying override gives
+ * the action, else spec.validationFailureAction. The labels are the corpus's namespace label table
+ * entry of the group's name (none: empty), as the CLI passes NamespaceSelectorMap[GetNamespace()]
+ * (policy_processor.go:63). The fold is kpe_cli_summary's: an unscored fail is a warn; a fail is a
+ * warn when audit_warn is set and the resolved action is Audit. Without overrides the totals equal
+ * kpe_cli_summary over the per-rule sums. Host only. */
+kpe_status kpe_cli_summary_ns(const kpe_program* prog, const kpe_corpus* c, const kpe_ns_counts* counts,
+                              int audit_warn, kpe_cli_totals* out);
 
 /* PolicyReport results of one resource (pkg/utils/report/results.go:89-156,
  * EngineResponseToReportResults), as the JSON array encoding/json writes for

@@ -8,6 +8,7 @@ evaluation without a working gfx950 device raises KpeError.
 """
 from ._lib import KpeError, lib_path, load  # noqa: F401
 from .engine import (  # noqa: F401
+    NS_COUNT_FIELDS,
     SEL,
     SEL_RESPONSES,
     SUMMARY_FIELDS,
@@ -29,6 +30,8 @@ from .engine import (  # noqa: F401
     RuleResponse,
     RuleStatus,
     cli_summary,
+    cli_summary_ns,
+    namespace_counts,
     report_results,
     row_summaries,
     synth_ns_labels,
@@ -49,6 +52,8 @@ __all__ = [
     "RuleStatus",
     "report_results",
     "cli_summary",
+    "cli_summary_ns",
+    "namespace_counts",
     "row_summaries",
     "synth_ns_labels",
     "synth_resources",

@@ -89,6 +89,21 @@ def load():
     L.kpe_fetch_row_summaries.restype = ctypes.c_int
     L.kpe_row_summaries_host.argtypes = [vp, vp, ctypes.c_uint64, vp]
     L.kpe_row_summaries_host.restype = ctypes.c_int
+    L.kpe_corpus_num_namespaces.argtypes = [vp]
+    L.kpe_corpus_num_namespaces.restype = i64
+    L.kpe_corpus_namespace.argtypes = [vp, i64]
+    L.kpe_corpus_namespace.restype = cp
+    L.kpe_corpus_row_namespaces.argtypes = [vp, vp]
+    L.kpe_corpus_row_namespaces.restype = ctypes.c_int
+    L.kpe_corpus_namespace_rows.argtypes = [vp, vp]
+    L.kpe_corpus_namespace_rows.restype = ctypes.c_int
+    L.kpe_fetch_namespace_counts.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp]
+    L.kpe_fetch_namespace_counts.restype = ctypes.c_int
+    L.kpe_namespace_counts_host.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp]
+    L.kpe_namespace_counts_host.restype = ctypes.c_int
+    L.kpe_cli_summary_ns.argtypes = [vp, vp, vp, i32, ctypes.POINTER(CliTotals)]
+    L.kpe_cli_summary_ns.restype = ctypes.c_int
+    L.kpe_debug_ns_counts_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     L.kpe_evaluate_sharded.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), i32, vp, vp, ctypes.POINTER(Counts)]
     L.kpe_fetch.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(Counts)]
     L.kpe_pss_check_id.argtypes = [i32]

@@ -2062,4 +2062,185 @@ extern "C" hipError_t kpe_launch_row_summary(const uint8_t* v, uint32_t R, uint6
     hipLaunchKernelGGL(kpe_row_summary_kernel<false>, grid, dim3(256), 0, s, v, R, row0, nrows, rpg, unscored, out);
   return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------
+// Per-namespace rule counts (kpe_fetch_namespace_counts): the verdict matrix grouped by the row's
+// namespace, 6 uint32 counters per (namespace, rule): pass, fail, warn, error, skip, undecided (raw
+// verdict codes; KPE_NA and codes outside the alphabet are not counted). The inverted-index form:
+// the host sorts the row ids by namespace once per corpus (`rows`) and cuts each namespace into
+// work items of at most kNsChunk rows (KpeNsItem). A block takes one item at a time, so every
+// contribution it sums has the same namespace, and counts in registers: a counter is a 10-bit
+// field of a 64-bit word (an item has at most 1023 rows, so no field overflows, in a lane or in a
+// sum over the block). Memory sees at most one add per (namespace, rule, counter) per item, and
+// only for non-zero counters: a plain store when the namespace is one item (the window is zeroed
+// before the launch), an integer atomic add otherwise. Integer adds only: the table is exact and
+// does not depend on the schedule.
+constexpr uint32_t kNsChunk = 512;    // rows per work item (<= 1023: the 10-bit fields)
+constexpr uint32_t kNsGrid = 2048;    // persistent blocks (8 per CU)
+constexpr uint32_t kNsNarrow = 16;    // R below this: one row per lane (kpe_ns_count_narrow_kernel)
+constexpr uint32_t kNsLdsUnits = 128; // column units a block sums in LDS (wider tiles: one lane per unit, no LDS)
+constexpr uint32_t kNsBatch = 8;      // row loads a lane keeps in flight
+static_assert(kNsChunk <= 1023u, "10-bit counters");
+
+namespace {
+// verdict code -> its 10-bit field of the packed counters (0 for codes that are not counted).
+// Code -> field: PASS 0, FAIL 1, WARN 2, ERROR 3, SKIP 4, UNDECIDED (7) 5
+__device__ __forceinline__ uint64_t ns_inc(uint32_t x) {
+  const uint32_t f = x < 8u ? (0x5F43210Fu >> (4u * x)) & 15u : 15u;
+  return f < 6u ? (uint64_t)1 << (10u * f) : (uint64_t)0;
+}
+__device__ __forceinline__ void ns_emit(uint32_t* __restrict__ o, uint32_t c, bool single) {
+  if (!c) return;
+  if (single) *o = c;
+  else atomicAdd(o, c);
+}
+}  // namespace
+
+// R >= kNsNarrow. The row is cut into units of VEC columns (VEC = 4 when R is a multiple of 4: a
+// unit is one aligned 32-bit load, and a word of four KPE_NA cells is passed over; VEC = 1
+// otherwise) and the units into tiles of W = min(units, 256). Thread t owns unit t % W of the tile
+// and the item's rows t / W, t / W + 256 / W, ...: lanes of a wave lie along the row (coalesced
+// loads, different counters). With one slice (W > 128) a lane's counters are final and go to memory
+// from registers; otherwise the slices are summed in LDS first (a lane's at most 6 * VEC non-zero
+// counters, different words for different lanes of a slice).
+template <uint32_t VEC>
+__global__ void __launch_bounds__(256) kpe_ns_count_kernel(const uint8_t* __restrict__ v, uint32_t R,
+                                                           const uint32_t* __restrict__ rows,
+                                                           const KpeNsItem* __restrict__ items, uint32_t nitems,
+                                                           uint32_t g0, uint32_t* __restrict__ out) {
+  __shared__ uint32_t s_cnt[kNsLdsUnits * 4u * 6u];
+  const uint32_t t = threadIdx.x;
+  const uint32_t units = R / VEC;  // VEC divides R
+  const uint32_t W = units < 256u ? units : 256u;
+  const uint32_t slices = 256u / W;
+  const uint32_t u = t % W, sl = t / W;
+  const bool lds = slices > 1u;  // then W <= kNsLdsUnits
+  if (lds) {
+    for (uint32_t i = t; i < W * VEC * 6u; i += 256u) s_cnt[i] = 0u;
+    __syncthreads();
+  }
+  for (uint32_t it = blockIdx.x; it < nitems; it += gridDim.x) {
+    const KpeNsItem item = items[it];
+    uint32_t* __restrict__ o = out + (size_t)(item.g - g0) * R * 6u;
+    const bool single = item.single != 0u;
+    for (uint32_t u0 = 0; u0 < units; u0 += W) {
+      const uint32_t uu = u0 + u;
+      const bool on = sl < slices && uu < units;
+      uint64_t acc[VEC];
+#pragma unroll
+      for (uint32_t j = 0; j < VEC; ++j) acc[j] = 0;
+      if (on) {
+        const uint8_t* __restrict__ base = v + (size_t)uu * VEC;
+        // the unit of one row: a 32-bit word of four cells, or one cell
+        auto load = [&](uint32_t row) -> uint32_t {
+          const uint8_t* p = base + (size_t)row * R;
+          return VEC == 4u ? *reinterpret_cast<const uint32_t*>(p) : (uint32_t)p[0];
+        };
+        auto count = [&](uint32_t w) {
+          if (w == 0u) return;  // KPE_NA cells (a word of four of them): nothing to count
+#pragma unroll
+          for (uint32_t j = 0; j < VEC; ++j) acc[j] += ns_inc((w >> (8u * j)) & 0xFFu);
+        };
+        // kNsBatch rows' loads are issued before the first is counted (the rows are a gather)
+        uint32_t i = item.begin + sl;
+        for (; i + (kNsBatch - 1u) * slices < item.end; i += kNsBatch * slices) {
+          uint32_t w[kNsBatch];
+#pragma unroll
+          for (uint32_t b = 0; b < kNsBatch; ++b) w[b] = load(rows[i + b * slices]);
+#pragma unroll
+          for (uint32_t b = 0; b < kNsBatch; ++b) count(w[b]);
+        }
+        for (; i < item.end; i += slices) count(load(rows[i]));
+      }
+      if (!lds) {
+        if (on) {
+#pragma unroll
+          for (uint32_t j = 0; j < VEC; ++j)
+#pragma unroll
+            for (uint32_t k = 0; k < 6u; ++k)
+              ns_emit(o + ((size_t)uu * VEC + j) * 6u + k, (uint32_t)(acc[j] >> (10u * k)) & 1023u, single);
+        }
+        continue;
+      }
+      if (on) {
+#pragma unroll
+        for (uint32_t j = 0; j < VEC; ++j)
+#pragma unroll
+          for (uint32_t k = 0; k < 6u; ++k) {
+            const uint32_t c = (uint32_t)(acc[j] >> (10u * k)) & 1023u;
+            if (c) atomicAdd(&s_cnt[(u * VEC + j) * 6u + k], c);
+          }
+      }
+      __syncthreads();
+      const uint32_t wn = (units - u0 < W ? units - u0 : W) * VEC * 6u;  // this tile's counters
+      for (uint32_t i = t; i < wn; i += 256u) {
+        const uint32_t c = s_cnt[i];
+        if (c) {
+          s_cnt[i] = 0u;
+          ns_emit(o + (size_t)u0 * VEC * 6u + i, c, single);
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// R < kNsNarrow (the C2 shape, R = 3): one row per lane, the row's R bytes, one packed register
+// per column. The columns' registers are summed over the wave with shuffles and over the four
+// waves through LDS (4 x R words): no atomics on a few hot LDS words.
+__global__ void __launch_bounds__(256) kpe_ns_count_narrow_kernel(const uint8_t* __restrict__ v, uint32_t R,
+                                                                  const uint32_t* __restrict__ rows,
+                                                                  const KpeNsItem* __restrict__ items, uint32_t nitems,
+                                                                  uint32_t g0, uint32_t* __restrict__ out) {
+  __shared__ uint64_t s_part[4][kNsNarrow];
+  const uint32_t t = threadIdx.x;
+  for (uint32_t it = blockIdx.x; it < nitems; it += gridDim.x) {
+    const KpeNsItem item = items[it];
+    uint64_t acc[kNsNarrow - 1u];
+#pragma unroll
+    for (uint32_t c = 0; c < kNsNarrow - 1u; ++c) acc[c] = 0;
+    for (uint32_t i = item.begin + t; i < item.end; i += 256u) {
+      const uint8_t* __restrict__ p = v + (size_t)rows[i] * R;
+#pragma unroll
+      for (uint32_t c = 0; c < kNsNarrow - 1u; ++c)
+        if (c < R) acc[c] += ns_inc(p[c]);
+    }
+#pragma unroll
+    for (uint32_t c = 0; c < kNsNarrow - 1u; ++c) {
+      if (c < R) {  // uniform
+        uint64_t a = acc[c];
+#pragma unroll
+        for (uint32_t d = 32u; d; d >>= 1) {
+          const uint32_t lo = __shfl_xor((int)(uint32_t)a, (int)d, 64), hi = __shfl_xor((int)(uint32_t)(a >> 32), (int)d, 64);
+          a += (uint64_t)lo | ((uint64_t)hi << 32);
+        }
+        if ((t & 63u) == 0u) s_part[t >> 6][c] = a;
+      }
+    }
+    __syncthreads();
+    if (t < R * 6u) {
+      const uint32_t c = t / 6u, k = t - c * 6u;
+      const uint64_t a = s_part[0][c] + s_part[1][c] + s_part[2][c] + s_part[3][c];
+      ns_emit(out + (size_t)(item.g - g0) * R * 6u + t, (uint32_t)(a >> (10u * k)) & 1023u, item.single != 0u);
+    }
+    __syncthreads();
+  }
+}
+
+// items: the work items of groups [g0, g0 + ng) (every item.g lies in it, every rows[] entry of
+// [begin, end) is a row of the matrix); out: ng x R x 6 words, zeroed by the caller on s.
+extern "C" hipError_t kpe_launch_ns_counts(const uint8_t* v, uint32_t R, const uint32_t* rows, const KpeNsItem* items,
+                                           uint64_t nitems, uint32_t g0, uint32_t* out, hipStream_t s) {
+  if (!nitems || !R) return hipSuccess;
+  if (nitems > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)std::min<uint64_t>(nitems, kNsGrid));
+  if (R < kNsNarrow)
+    hipLaunchKernelGGL(kpe_ns_count_narrow_kernel, grid, dim3(256), 0, s, v, R, rows, items, (uint32_t)nitems, g0, out);
+  else if (R % 4u == 0u)
+    hipLaunchKernelGGL(kpe_ns_count_kernel<4u>, grid, dim3(256), 0, s, v, R, rows, items, (uint32_t)nitems, g0, out);
+  else
+    hipLaunchKernelGGL(kpe_ns_count_kernel<1u>, grid, dim3(256), 0, s, v, R, rows, items, (uint32_t)nitems, g0, out);
+  return hipGetLastError();
+}
+extern "C" uint32_t kpe_ns_chunk_rows(void) { return kNsChunk; }
 #endif  // !KPE_VM_ONLY

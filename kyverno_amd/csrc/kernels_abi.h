@@ -34,6 +34,13 @@ struct KpePat {
   uint32_t kind, off, len, pad;  // literal (or full pattern for PK_GLOB) = pat_bytes[off, off+len)
 };
 
+// One work item of the per-namespace count kernels (kpe_launch_ns_counts, kernels.hip): rows
+// [begin, end) of the corpus's rows-by-namespace list, all of namespace group g, at most
+// kpe_ns_chunk_rows() of them. single: the group's only item (its counters are stored, not added).
+struct KpeNsItem {
+  uint32_t g, begin, end, single;
+};
+
 struct PredJob {
   uint32_t domain;
   uint32_t pat0, npat;  // patterns [pat0, pat0+npat) of the pattern table

@@ -62,6 +62,9 @@ extern "C" hipError_t kpe_launch_select_scatter(const uint8_t* v, uint64_t cells
                                                 uint64_t* out_cells, uint8_t* out_v, hipStream_t s);
 extern "C" hipError_t kpe_launch_row_summary(const uint8_t* v, uint32_t R, uint64_t row0, uint64_t nrows,
                                              const uint8_t* unscored, uint32_t* out, hipStream_t s);
+extern "C" hipError_t kpe_launch_ns_counts(const uint8_t* v, uint32_t R, const uint32_t* rows, const KpeNsItem* items,
+                                           uint64_t nitems, uint32_t g0, uint32_t* out, hipStream_t s);
+extern "C" uint32_t kpe_ns_chunk_rows(void);
 
 namespace {
 thread_local std::string g_err;
@@ -173,6 +176,9 @@ struct kpe_device {
   bool stage_busy[2] = {};
   int stage_cur = 0;
   double up_alloc_s = 0, up_copy_s = 0;  // KPE_DEBUG upload breakdown (under mu)
+  // kpe_fetch_namespace_counts with timing on: the last call's kernel time (HIP events) and the
+  // last rows-by-namespace index build + upload (host clock)
+  double ns_kernel_ms = 0, ns_index_ms = 0;
   hipEvent_t get_ev() {
     if (!pool.empty()) {
       hipEvent_t e = pool.back();
@@ -285,15 +291,29 @@ struct DeviceCorpus {
   bool codes_ready = false;
   Binding bind;
   bool has_masks = false;
+  // rows by namespace group (kpe_fetch_namespace_counts): row ids sorted by group, the groups'
+  // work items (kernels_abi.h KpeNsItem), and on the host the first item of each group (G + 1)
+  DevBuf ns_rows, ns_items;
+  DevBuf ns_out;  // the counters of a small window (kpe_fetch_namespace_counts keeps up to 4 MiB)
+  std::vector<uint64_t> ns_item_off;
+  bool ns_ready = false;
 };
 }  // namespace kpe
 
 struct kpe_program {
   std::unique_ptr<kpe::Program> p;
 };
+// Namespace groups of a corpus (kpe_corpus_num_namespaces): the ids of the D_NS dictionary, plus
+// one for "" when no row interned it
+struct NsGroups {
+  std::vector<std::string> names;
+  uint32_t empty = 0;  // the group of ""
+};
 struct kpe_corpus {
   std::unique_ptr<kpe::Corpus> c;
   std::unique_ptr<kpe::DeviceCorpus> d;
+  mutable std::mutex ns_mu;
+  mutable std::unique_ptr<NsGroups> ns;  // built on first use
 };
 
 extern "C" {
@@ -2243,6 +2263,177 @@ kpe_status kpe_fetch_row_summaries(kpe_device* dev, const kpe_program* prog, con
   return KPE_OK;
 }
 
+// ---- namespace groups and per-namespace rule counts -------------------------------------------
+static const NsGroups& ns_groups(const kpe_corpus* c) {
+  std::lock_guard<std::mutex> lk(c->ns_mu);
+  if (!c->ns) {
+    auto g = std::make_unique<NsGroups>();
+    const kpe::Dict& d = c->c->dict[D_NS];
+    for (uint32_t i = 0; i < d.size(); ++i) g->names.emplace_back(d.at(i));
+    const int64_t e = d.find("");
+    if (e < 0) g->names.emplace_back();
+    g->empty = e < 0 ? d.size() : (uint32_t)e;
+    c->ns = std::move(g);
+  }
+  return *c->ns;
+}
+// the group of row i: its r_nsa id; a row without a namespace string belongs to ""
+static inline uint32_t ns_group_of(const kpe::Corpus& C, const NsGroups& G, size_t i) {
+  const uint32_t id = i < C.r_nsa.size() ? C.r_nsa[i] : KPE_NO_STR;
+  return id < C.dict[D_NS].size() ? id : G.empty;
+}
+
+int64_t kpe_corpus_num_namespaces(const kpe_corpus* c) { return c ? (int64_t)ns_groups(c).names.size() : 0; }
+const char* kpe_corpus_namespace(const kpe_corpus* c, int64_t g) {
+  if (!c) return nullptr;
+  const NsGroups& G = ns_groups(c);
+  return g >= 0 && (size_t)g < G.names.size() ? G.names[(size_t)g].c_str() : nullptr;
+}
+kpe_status kpe_corpus_row_namespaces(const kpe_corpus* c, uint32_t* out) {
+  if (!c || (!out && c->c->n)) return fail(KPE_E_INVALID, "kpe_corpus_row_namespaces: null argument");
+  const NsGroups& G = ns_groups(c);
+  for (int64_t i = 0; i < c->c->n; ++i) out[i] = ns_group_of(*c->c, G, (size_t)i);
+  return KPE_OK;
+}
+kpe_status kpe_corpus_namespace_rows(const kpe_corpus* c, uint64_t* out) {
+  if (!c || !out) return fail(KPE_E_INVALID, "kpe_corpus_namespace_rows: null argument");
+  const NsGroups& G = ns_groups(c);
+  std::fill(out, out + G.names.size(), (uint64_t)0);
+  for (int64_t i = 0; i < c->c->n; ++i) ++out[ns_group_of(*c->c, G, (size_t)i)];
+  return KPE_OK;
+}
+
+static inline void ns_count_add(kpe_ns_counts& o, uint8_t v) {
+  switch (v) {
+    case KPE_PASS: ++o.pass; break;
+    case KPE_FAIL: ++o.fail; break;
+    case KPE_WARN: ++o.warn; break;
+    case KPE_ERROR: ++o.error; break;
+    case KPE_SKIP: ++o.skip; break;
+    case KPE_UNDECIDED: ++o.undecided; break;
+    default: break;  // KPE_NA: no RuleResponse
+  }
+}
+
+// the argument checks the device call and its host twin share (before any device call)
+static kpe_status ns_window_check(const kpe_program* prog, const kpe_corpus* c, uint64_t g0, uint64_t ng,
+                                  const void* out) {
+  if (!prog || !c || (ng && !out)) return fail(KPE_E_INVALID, "null argument");
+  const uint64_t G = ns_groups(c).names.size();
+  if (g0 > G || ng > G - g0) return fail(KPE_E_INVALID, "namespace groups past the corpus");
+  if ((uint64_t)c->c->n >= (1ull << 32)) return fail(KPE_E_LIMIT, "namespace counts hold at most 2^32 - 1 rows");
+  return KPE_OK;
+}
+
+kpe_status kpe_namespace_counts_host(const kpe_program* prog, const kpe_corpus* c, const uint8_t* verdicts,
+                                     uint64_t g0, uint64_t ng, kpe_ns_counts* out) {
+  if (kpe_status st = ns_window_check(prog, c, g0, ng, out)) return st;
+  const size_t R = prog->p->rules.size();
+  if (!ng || !R) return KPE_OK;
+  const kpe::Corpus& C = *c->c;
+  if (!verdicts && C.n) return fail(KPE_E_INVALID, "null argument");
+  const NsGroups& G = ns_groups(c);
+  memset(out, 0, (size_t)ng * R * sizeof(kpe_ns_counts));
+  for (int64_t i = 0; i < C.n; ++i) {
+    const uint64_t g = ns_group_of(C, G, (size_t)i);
+    if (g < g0 || g - g0 >= ng) continue;
+    kpe_ns_counts* o = out + (size_t)(g - g0) * R;
+    const uint8_t* v = verdicts + (size_t)i * R;
+    for (size_t r = 0; r < R; ++r) ns_count_add(o[r], v[r]);
+  }
+  return KPE_OK;
+}
+
+// The corpus's rows-by-namespace index, once per upload: a counting sort of the row ids by group
+// (4 bytes per row) and each group's rows cut into work items of at most kpe_ns_chunk_rows() rows.
+static kpe_status ns_index(kpe_device* dev, const kpe_corpus* c, hipStream_t s) {
+  kpe::DeviceCorpus& D = *c->d;
+  if (D.ns_ready) return KPE_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  const kpe::Corpus& C = *c->c;
+  const NsGroups& G = ns_groups(c);
+  const size_t ngr = G.names.size(), n = (size_t)C.n;
+  const uint32_t chunk = kpe_ns_chunk_rows();
+  std::vector<uint32_t> off(ngr + 1, 0u), rows(n);
+  for (size_t i = 0; i < n; ++i) ++off[ns_group_of(C, G, i) + 1u];
+  for (size_t g = 0; g < ngr; ++g) off[g + 1] += off[g];
+  {
+    std::vector<uint32_t> cur(off.begin(), off.end() - 1);
+    for (size_t i = 0; i < n; ++i) rows[cur[ns_group_of(C, G, i)]++] = (uint32_t)i;  // ascending rows per group
+  }
+  std::vector<KpeNsItem> items;
+  D.ns_item_off.assign(ngr + 1, 0);
+  for (size_t g = 0; g < ngr; ++g) {
+    D.ns_item_off[g] = items.size();
+    const bool single = off[g + 1] - off[g] <= chunk;
+    for (uint32_t b = off[g]; b < off[g + 1]; b += chunk)
+      items.push_back(KpeNsItem{(uint32_t)g, b, std::min(b + chunk, off[g + 1]), single ? 1u : 0u});
+  }
+  D.ns_item_off[ngr] = items.size();
+  HIPCHK(D.ns_rows.ensure(rows.size() * 4));
+  HIPCHK(D.ns_items.ensure(items.size() * sizeof(KpeNsItem)));
+  if (!rows.empty()) HIPCHK(hipMemcpyAsync(D.ns_rows.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, s));
+  if (!items.empty())
+    HIPCHK(hipMemcpyAsync(D.ns_items.p, items.data(), items.size() * sizeof(KpeNsItem), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));  // rows / items are this call's
+  D.ns_ready = true;
+  dev->ns_index_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return KPE_OK;
+}
+
+kpe_status kpe_fetch_namespace_counts(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, uint64_t g0,
+                                      uint64_t ng, kpe_ns_counts* out) {
+  if (!dev) return fail(KPE_E_INVALID, "null argument");
+  if (kpe_status st = ns_window_check(prog, c, g0, ng, out)) return st;
+  const size_t R = prog->p->rules.size();
+  if (!ng || !R) return KPE_OK;
+  if (!c->d) return fail(KPE_E_STATE, "corpus not uploaded");
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  auto& B = c->d->bind;
+  if (B.prog != prog->p.get()) return fail(KPE_E_STATE, "no evaluation of this program on this corpus");
+  if (c->d->ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  hipStream_t s = B.last ? B.last : dev->stream;
+  if (kpe_status st = ns_index(dev, c, s)) return st;
+  kpe::DeviceCorpus& D = *c->d;
+  static_assert(sizeof(kpe_ns_counts) == 24, "6 words per (group, rule)");
+  const size_t out_bytes = (size_t)ng * R * sizeof(kpe_ns_counts);
+  // the window's counters: a table of up to kNsKeepBytes stays with the corpus (a consumer asks
+  // for the same small table after every evaluation: no allocation per call); a larger window is
+  // this call's scratch, freed on every return path
+  constexpr size_t kNsKeepBytes = 4u << 20;
+  DevBuf own;
+  DevBuf& scratch = out_bytes <= kNsKeepBytes ? D.ns_out : own;
+  HIPCHK(scratch.ensure(out_bytes));
+  HIPCHK(hipMemsetAsync(scratch.p, 0, out_bytes, s));
+  const uint64_t i0 = D.ns_item_off[g0], i1 = D.ns_item_off[g0 + ng];  // the window's work items
+  hipEvent_t ea = nullptr, eb = nullptr;
+  if (dev->timing) {
+    ea = dev->get_ev(), eb = dev->get_ev();
+    HIPCHK(hipEventRecord(ea, s));
+  }
+  HIPCHK(kpe_launch_ns_counts(B.verdicts.as<uint8_t>(), (uint32_t)R, D.ns_rows.as<uint32_t>(),
+                              D.ns_items.as<KpeNsItem>() + i0, i1 - i0, (uint32_t)g0, scratch.as<uint32_t>(), s));
+  if (dev->timing) HIPCHK(hipEventRecord(eb, s));
+  HIPCHK(hipMemcpyAsync(out, scratch.p, out_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (dev->timing) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ea, eb) == hipSuccess) dev->ns_kernel_ms = ms;
+    dev->pool.push_back(ea), dev->pool.push_back(eb);
+  }
+  return KPE_OK;
+}
+// Diagnostic (not in kpe.h; scripts/ns_counts_bench.py): with kpe_device_set_timing on, the kernel
+// time of the last kpe_fetch_namespace_counts and the last index build + upload, in ms
+kpe_status kpe_debug_ns_counts_ms(kpe_device* dev, double* kernel_ms, double* index_ms) {
+  if (!dev) return fail(KPE_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(dev->mu);
+  if (kernel_ms) *kernel_ms = dev->ns_kernel_ms;
+  if (index_ms) *index_ms = dev->ns_index_ms;
+  return KPE_OK;
+}
+
 // ---- failing paths of pattern cells (report time) ---------------------------------------------
 // The foreach entry that decided a FAIL / ERROR cell from its trace words (schema.h FT_*): the
 // entry index in Program::fe_reports, or -1 (no valid path)
@@ -2462,6 +2653,62 @@ kpe_status kpe_cli_summary(const kpe_program* prog, const kpe_counts* counts, in
     out->warn += m * counts[r].warn;
     if (!rr.scored || (audit_warn && rr.audit)) out->warn += m * counts[r].fail;
     else out->fail += m * counts[r].fail;
+  }
+  return KPE_OK;
+}
+
+// kpe_cli_summary with the action resolved per namespace group (engineresponse.go:196-225 through
+// kpe::vfa_audit): counts is the G x R table of kpe_fetch_namespace_counts / kpe_namespace_counts_host.
+kpe_status kpe_cli_summary_ns(const kpe_program* prog, const kpe_corpus* c, const kpe_ns_counts* counts,
+                              int audit_warn, kpe_cli_totals* out) {
+  if (!prog || !c || !counts || !out) return fail(KPE_E_INVALID, "null argument");
+  const kpe::Program& P = *prog->p;
+  const kpe::Corpus& C = *c->c;
+  const NsGroups& G = ns_groups(c);
+  const size_t R = P.rules.size();
+  *out = kpe_cli_totals{};
+  std::vector<int8_t> audit(P.vfa_overrides.size());  // per policy, for this group: -1 not resolved yet
+  std::vector<std::pair<std::string, std::string>> labels;
+  for (size_t g = 0; g < G.names.size(); ++g) {
+    std::fill(audit.begin(), audit.end(), (int8_t)-1);
+    bool have_labels = false;
+    for (size_t r = 0; r < R; ++r) {
+      const kpe::RuleReport& rr = P.reports[r];
+      const uint64_t m = rr.name_mult;
+      if (!m) continue;
+      const kpe_ns_counts& k = counts[g * R + r];
+      out->pass += m * k.pass;
+      out->error += m * k.error;
+      out->skip += m * k.skip;
+      out->warn += m * k.warn;
+      if (!k.fail) continue;
+      bool warn = !rr.scored;
+      if (!warn && audit_warn) {
+        if (!rr.overrides || rr.policy >= audit.size()) {
+          warn = rr.audit;
+        } else {
+          if (audit[rr.policy] < 0) {
+            if (!have_labels) {  // PolicyContext.NamespaceLabels of the group's name (none: empty)
+              labels.clear();
+              auto it = C.nsl_index.find(G.names[g]);
+              if (it != C.nsl_index.end() && (size_t)it->second + 1 < C.nsl_off.size())
+                for (uint32_t j = C.nsl_off[it->second]; j < C.nsl_off[it->second + 1]; ++j)
+                  labels.emplace_back(std::string(C.dict[D_LABK].at(C.nsl_k[j])), std::string(C.dict[D_LABV].at(C.nsl_v[j])));
+              std::stable_sort(labels.begin(), labels.end(),
+                               [](const auto& a, const auto& b) { return a.first < b.first; });
+              // a repeated key of the table's JSON object: the last one is the map's value
+              for (size_t j = 0; j + 1 < labels.size();)
+                if (labels[j].first == labels[j + 1].first) labels.erase(labels.begin() + (long)j);
+                else ++j;
+              have_labels = true;
+            }
+            audit[rr.policy] = kpe::vfa_audit(P, rr.policy, rr.audit, G.names[g], labels) ? 1 : 0;
+          }
+          warn = audit[rr.policy] != 0;
+        }
+      }
+      (warn ? out->warn : out->fail) += m * k.fail;
+    }
   }
   return KPE_OK;
 }

@@ -2959,6 +2959,116 @@ class Lowerer {
 
 Program::~Program() = default;
 
+namespace {
+// spec.validationFailureActionOverrides as encoding/json decodes it: `namespaces: null` (or absent)
+// is a nil slice, `namespaces: []` an empty one; `namespaceSelector: null` a nil selector
+std::vector<VfaOverride> parse_vfa_overrides(const JV* ovr) {
+  std::vector<VfaOverride> out;
+  if (!ovr || ovr->t != JV::Arr) return out;
+  for (const JV& e : ovr->a) {
+    VfaOverride v;
+    v.action = sv(e.get("action"));
+    const JV* nss = e.get("namespaces");
+    v.ns_present = nss && nss->t == JV::Arr;
+    v.namespaces = svl(nss);
+    const JV* sel = e.get("namespaceSelector");
+    if (sel && sel->t != JV::Null) {
+      v.has_selector = true;
+      const JV* ml = sel->get("matchLabels");
+      const JV* me = sel->get("matchExpressions");
+      if (sel->t != JV::Obj || (ml && ml->t != JV::Null && ml->t != JV::Obj) ||
+          (me && me->t != JV::Null && me->t != JV::Arr))
+        v.selector_malformed = true;
+      if (ml && ml->t == JV::Obj)
+        for (auto& kv : ml->o) {
+          if (kv.second.t != JV::Str) v.selector_malformed = true;
+          v.match_labels.emplace_back(kv.first, kv.second.s);
+        }
+      if (me && me->t == JV::Arr)
+        for (const JV& x : me->a)
+          v.match_exprs.push_back({sv(x.get("key")), sv(x.get("operator")), svl(x.get("values"))});
+    }
+    out.push_back(std::move(v));
+  }
+  return out;
+}
+
+using LabelSet = std::vector<std::pair<std::string, std::string>>;
+const std::string* label_get(const LabelSet& labels, const std::string& k) {
+  for (auto& kv : labels)
+    if (kv.first == k) return &kv.second;
+  return nullptr;
+}
+
+// CheckSelector (pkg/utils/match/labels.go:10-24) of a non-nil selector: ReplaceInSelector
+// (pkg/engine/wildcards/wildcards.go:13-58: a matchLabels entry with a wildcard becomes the first
+// label it matches, or itself with '*' and '?' replaced by '0'), metav1.LabelSelectorAsSelector
+// (an error is false) and Matches. `labels` is walked in key order where Go's map order is random:
+// the choice only shows when several labels match one entry and differ in validity.
+bool check_selector(const VfaOverride& v, const LabelSet& labels) {
+  if (v.selector_malformed) return false;
+  std::map<std::string, std::string> want;  // the replaced matchLabels
+  for (auto& kv : v.match_labels) {
+    std::string k = kv.first, val = kv.second;
+    if (has_wildcard(k) || has_wildcard(val)) {
+      bool found = false;
+      for (auto& l : labels)
+        if (glob_host(k, l.first) && glob_host(val, l.second)) {
+          k = l.first, val = l.second, found = true;
+          break;
+        }
+      if (!found) {
+        for (auto& c : k)
+          if (c == '*' || c == '?') c = '0';
+        for (auto& c : val)
+          if (c == '*' || c == '?') c = '0';
+      }
+    }
+    want[k] = val;
+  }
+  // LabelSelectorAsSelector: every requirement must build (labels.NewRequirement)
+  for (auto& kv : want)
+    if (!qualified_name_ok(kv.first) || !label_value_ok(kv.second)) return false;
+  for (auto& x : v.match_exprs) {
+    if (!qualified_name_ok(x.key)) return false;
+    if (x.op == "In" || x.op == "NotIn") {
+      if (x.values.empty()) return false;
+    } else if (x.op == "Exists" || x.op == "DoesNotExist") {
+      if (!x.values.empty()) return false;
+    } else {
+      return false;
+    }
+    for (auto& s : x.values)
+      if (!label_value_ok(s)) return false;
+  }
+  for (auto& kv : want) {
+    const std::string* have = label_get(labels, kv.first);
+    if (!have || *have != kv.second) return false;
+  }
+  for (auto& x : v.match_exprs) {
+    const std::string* have = label_get(labels, x.key);
+    const bool in = have && std::find(x.values.begin(), x.values.end(), *have) != x.values.end();
+    if (x.op == "In" && !in) return false;
+    if (x.op == "NotIn" && in) return false;
+    if (x.op == "Exists" && !have) return false;
+    if (x.op == "DoesNotExist" && have) return false;
+  }
+  return true;
+}
+}  // namespace
+
+bool vfa_audit(const Program& P, uint32_t policy, bool spec_audit, const std::string& ns, const LabelSet& labels) {
+  if (policy >= P.vfa_overrides.size()) return spec_audit;
+  for (const VfaOverride& v : P.vfa_overrides[policy]) {
+    if (v.action != "audit" && v.action != "enforce" && v.action != "Audit" && v.action != "Enforce") continue;
+    const bool audit = !(v.action == "Enforce" || v.action == "enforce");
+    if (!v.ns_present && v.has_selector && check_selector(v, labels)) return audit;
+    for (const std::string& g : v.namespaces)
+      if (glob_host(g, ns) && (!v.has_selector || check_selector(v, labels))) return audit;
+  }
+  return spec_audit;
+}
+
 std::unique_ptr<Program> compile_policies(const char* json, size_t len, const char* exceptions, size_t exc_len,
                                           bool background) {
   JV root = parse_all(json, len);
@@ -2987,8 +3097,10 @@ std::unique_ptr<Program> compile_policies(const char* json, size_t len, const ch
     if (sev != "critical" && sev != "high" && sev != "medium" && sev != "low" && sev != "info") sev.clear();
     const std::string vfa = spec ? sv(spec->get("validationFailureAction")) : std::string();
     const JV* ovr = spec ? spec->get("validationFailureActionOverrides") : nullptr;
+    prog->vfa_overrides.push_back(parse_vfa_overrides(ovr));
     for (size_t i = r0; i < prog->reports.size(); ++i) {
       RuleReport& rr = prog->reports[i];
+      rr.policy = (uint32_t)pi;
       rr.audit = !(vfa == "Enforce" || vfa == "enforce");
       rr.overrides = ovr && ovr->t == JV::Arr && !ovr->a.empty();
       rr.name_mult = 0;

@@ -115,6 +115,7 @@ struct RuleReport {
   bool has_validate = false;  // rule.HasValidate() (processor/result.go:42)
   bool audit = true;          // spec.validationFailureAction.Audit() (!Enforce, spec_types.go:31-37)
   bool overrides = false;     // spec.validationFailureActionOverrides non-empty (per-namespace action)
+  uint32_t policy = 0;        // index into Program::vfa_overrides (the rule's policy)
   uint32_t name_mult = 1;     // validate rules of the policy with this name (result.go:44 name match)
   bool pss = false;
   bool pss_excl = false;      // podSecurity.exclude or a podSecurity PolicyException (fail messages not rendered)
@@ -160,9 +161,26 @@ struct RuleReport {
   uint32_t fe0 = 0, nfe = 0;
 };
 
+// One entry of spec.validationFailureActionOverrides (api/kyverno/v1/spec_types.go:43-48), kept as
+// written for GetValidationFailureAction (pkg/engine/api/engineresponse.go:196-225).
+struct VfaOverride {
+  std::string action;                   // valid: audit, enforce, Audit, Enforce (spec_types.go:39-41)
+  bool ns_present = false;              // `namespaces` decodes to a non-nil slice (an empty list is not nil)
+  std::vector<std::string> namespaces;  // go-wildcard globs on the resource's namespace
+  bool has_selector = false;            // namespaceSelector is not nil
+  bool selector_malformed = false;      // it would not decode as a metav1.LabelSelector: never holds
+  std::vector<std::pair<std::string, std::string>> match_labels;
+  struct Expr {
+    std::string key, op;
+    std::vector<std::string> values;
+  };
+  std::vector<Expr> match_exprs;
+};
+
 struct Program {
   std::vector<std::string> rule_names;  // "<policy>/<rule>"
   std::vector<RuleReport> reports;      // per rule, same order
+  std::vector<std::vector<VfaOverride>> vfa_overrides;  // per policy (RuleReport::policy), in order
   std::vector<KpeRule> rules;
   std::vector<KpeFilter> filters;
   std::vector<uint32_t> fterms;  // term indices of the filters
@@ -196,6 +214,12 @@ struct CompileError : std::runtime_error {
 };
 std::unique_ptr<Program> compile_policies(const char* json, size_t len, const char* exceptions = nullptr,
                                           size_t exc_len = 0, bool background = false);
+
+// GetValidationFailureAction(...).Audit() (engineresponse.go:196-225) of policy `policy` for a
+// resource of namespace `ns` whose namespace labels are `labels` (sorted by key): the first
+// applying override's action, else `spec_audit` (spec.validationFailureAction).
+bool vfa_audit(const Program& P, uint32_t policy, bool spec_audit, const std::string& ns,
+               const std::vector<std::pair<std::string, std::string>>& labels);
 
 // variables.SubstituteAll of a rule message over one resource (program.cpp): false when the
 // message holds variables outside the restated `request.object` path grammar; *nonstring: the

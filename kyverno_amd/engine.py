@@ -181,6 +181,27 @@ class Corpus:
         """64-bit digest of the columnar encoding (kpe_corpus_digest)."""
         return int(load().kpe_corpus_digest(self.h))
 
+    @property
+    def namespaces(self) -> List[str]:
+        """Names of the corpus's namespace groups (kpe_corpus_namespace), by group id. A resource's
+        group is its metadata.namespace (GetNamespace()); "" is the group of cluster-scoped
+        resources (a Namespace object included) and always exists."""
+        L = load()
+        return [L.kpe_corpus_namespace(self.h, g).decode(errors="surrogateescape")
+                for g in range(int(L.kpe_corpus_num_namespaces(self.h)))]
+
+    def row_namespaces(self) -> np.ndarray:
+        """The namespace group of every row (kpe_corpus_row_namespaces): (n,) uint32."""
+        out = np.zeros(self.n, dtype=np.uint32)
+        check(load().kpe_corpus_row_namespaces(self.h, out.ctypes.data if self.n else None))
+        return out
+
+    def namespace_rows(self) -> np.ndarray:
+        """Rows per namespace group (kpe_corpus_namespace_rows): (G,) uint64, summing to n."""
+        out = np.zeros(int(load().kpe_corpus_num_namespaces(self.h)), dtype=np.uint64)
+        check(load().kpe_corpus_namespace_rows(self.h, out.ctypes.data))
+        return out
+
     def upload(self, dev: Device):
         check(load().kpe_corpus_upload(dev.h, self.h))
         self.device = dev
@@ -399,6 +420,15 @@ class Engine:
         check(load().kpe_fetch_row_summaries(self.device.h, ps.h, corpus.h, row0, n, out.ctypes.data if n > 0 else None))
         return out
 
+    def namespace_counts(self, ps: PolicySet, corpus: Corpus, g0: int = 0, ng: Optional[int] = None) -> np.ndarray:
+        """Per-namespace rule counts of groups [g0, g0 + ng) of the last evaluation of ps on
+        corpus, reduced on the device (kpe_fetch_namespace_counts): (ng, R, 6) uint32, last axis
+        NS_COUNT_FIELDS (raw verdict codes: fail counts unscored fails too; NA is not counted)."""
+        n = _ns_window(corpus, g0, ng)
+        out = np.zeros((n, ps.num_rules, 6), dtype=np.uint32)
+        check(load().kpe_fetch_namespace_counts(self.device.h, ps.h, corpus.h, g0, n, out.ctypes.data if n else None))
+        return out
+
     def pattern_traces(self, ps: PolicySet, corpus: Corpus, cells) -> np.ndarray:
         """Failing-path records of pattern cells (kpe_pattern_traces) after an evaluation of ps on
         corpus: cells = flat indices row * R + column; returns (len(cells), KPE_TRACE_ROOTS,
@@ -574,4 +604,41 @@ def cli_summary(ps: PolicySet, counts: List[dict], audit_warn: bool = False) -> 
         arr[i].undecided = c.get("undecided", 0)
     out = CliTotals()
     check(load().kpe_cli_summary(ps.h, arr, 1 if audit_warn else 0, ctypes.byref(out)))
+    return {"pass": out.pass_, "fail": out.fail, "warn": out.warn, "error": out.error, "skip": out.skip}
+
+
+NS_COUNT_FIELDS = ("pass", "fail", "warn", "error", "skip", "undecided")  # kpe_ns_counts, in order
+
+
+def _ns_window(corpus: Corpus, g0: int, ng: Optional[int]) -> int:
+    if g0 < 0 or (ng is not None and ng < 0):
+        raise ValueError("namespace window: g0 and ng are not negative")
+    return max(int(load().kpe_corpus_num_namespaces(corpus.h)) - g0, 0) if ng is None else int(ng)
+
+
+def namespace_counts(ps: PolicySet, corpus: Corpus, verdicts, g0: int = 0, ng: Optional[int] = None) -> np.ndarray:
+    """Engine.namespace_counts over an (n, R) verdict matrix the caller holds (n = the corpus's
+    rows), through kpe_namespace_counts_host (no device call): (ng, R, 6) uint32."""
+    v = np.ascontiguousarray(verdicts, dtype=np.uint8)
+    R = ps.num_rules
+    if v.shape != (corpus.n, R):
+        raise ValueError("verdicts: one row per resource of the corpus, one cell per rule")
+    n = _ns_window(corpus, g0, ng)
+    out = np.zeros((n, R, 6), dtype=np.uint32)
+    check(load().kpe_namespace_counts_host(ps.h, corpus.h, v.ctypes.data if v.size else None, g0, n,
+                                           out.ctypes.data if n else None))
+    return out
+
+
+def cli_summary_ns(ps: PolicySet, corpus: Corpus, counts, audit_warn: bool = False) -> Dict[str, int]:
+    """`kyverno apply` totals (processor/result.go:34-68) from the (G, R, 6) per-namespace table of
+    every group of the corpus, the action resolved per namespace (kpe_cli_summary_ns): answers
+    --audit-warn for policies with validationFailureActionOverrides, which cli_summary refuses."""
+    k = np.ascontiguousarray(counts, dtype=np.uint32)
+    G = int(load().kpe_corpus_num_namespaces(corpus.h))
+    if k.shape != (G, ps.num_rules, 6):
+        raise ValueError("counts: (namespaces of the corpus, rules, 6)")
+    out = CliTotals()
+    buf = k if k.size else np.zeros(6, dtype=np.uint32)
+    check(load().kpe_cli_summary_ns(ps.h, corpus.h, buf.ctypes.data, 1 if audit_warn else 0, ctypes.byref(out)))
     return {"pass": out.pass_, "fail": out.fail, "warn": out.warn, "error": out.error, "skip": out.skip}

@@ -36,6 +36,38 @@ def rows_to_counts(rows) -> List[Dict[str, int]]:
     return [dict(zip(COUNT_FIELDS, (int(x) for x in r))) for r in rows]
 
 
+def merge_namespace_counts(parts):
+    """One per-namespace table from the shards' tables: parts is a sequence of (names, counts)
+    pairs, names = Corpus.namespaces of a shard and counts its (G_i, R, 6) table
+    (Engine.namespace_counts / kyverno_amd.namespace_counts). Every shard numbers its groups
+    itself, so the tables are merged by namespace name, not by id: host only, and an all-reduce
+    does not apply. Returns (names, counts): the names in first-seen order and a (G, R, 6) uint64
+    table (sums over shards can pass 32 bits)."""
+    import numpy as np
+
+    index: Dict[str, int] = {}
+    names: List[str] = []
+    tabs = []
+    for part_names, counts in parts:
+        k = np.asarray(counts)
+        if k.ndim != 3 or k.shape[0] != len(part_names) or k.shape[2] != 6:
+            raise ValueError("merge_namespace_counts: (names, (len(names), R, 6) counts) pairs")
+        if tabs and k.shape[1] != tabs[0][1].shape[1]:
+            raise ValueError("merge_namespace_counts: the shards' tables differ in their rule count")
+        ids = []
+        for nm in part_names:
+            if nm not in index:
+                index[nm] = len(names)
+                names.append(nm)
+            ids.append(index[nm])
+        tabs.append((np.asarray(ids, dtype=np.int64), k))
+    R = tabs[0][1].shape[1] if tabs else 0
+    out = np.zeros((len(names), R, 6), dtype=np.uint64)
+    for ids, k in tabs:
+        np.add.at(out, ids, k.astype(np.uint64))
+    return names, out
+
+
 def allreduce_counts(counts: Sequence[Dict[str, int]], device=None) -> List[Dict[str, int]]:
     """Sum per-rule counters over the default process group (RCCL on GPU ranks,
     gloo on CPU). One R x 6 int64 tensor; identity when not initialised."""
