@@ -1,6 +1,6 @@
 // Condition VM: preconditions / deny / foreach-deny of the compiled program (program.cpp cq::*)
-// evaluated per resource over the document tape. Device code included inside kernels.hip's
-// anonymous namespace (after patvm.inl, whose tape helpers it shares).
+// evaluated per resource over the document tape. Device code included by cond_kernel.inl inside
+// its anonymous namespace (after patvm.inl, whose tape helpers it shares).
 //
 // Restates, for the subset the compiler accepts:
 //   variables/evaluate.go:14-125      Evaluate / evaluateAnyAllConditions / evaluateOldConditions

@@ -1,4 +1,6 @@
-// Kernel argument structs shared by kernels.hip (device) and kpe_api.cpp (host).
+// Kernel argument structs shared by the kernel sources (*.hip, device) and kpe_api.cpp (host). No HIP
+// types here (the host check programs under scripts/ include it); the launchers are declared in
+// kernels_launch.h.
 #pragma once
 #include <stdint.h>
 
@@ -34,7 +36,7 @@ struct KpePat {
   uint32_t kind, off, len, pad;  // literal (or full pattern for PK_GLOB) = pat_bytes[off, off+len)
 };
 
-// One work item of the per-namespace count kernels (kpe_launch_ns_counts, kernels.hip): rows
+// One work item of the per-namespace count kernels (kpe_launch_ns_counts, results.hip): rows
 // [begin, end) of the corpus's rows-by-namespace list, all of namespace group g, at most
 // kpe_ns_chunk_rows() of them. single: the group's only item (its counters are stored, not added).
 struct KpeNsItem {
@@ -219,7 +221,7 @@ struct ScanArgs {
 #define KPE_PSF_MAXLEN 64u
 #define KPE_PSF_ENT0 (2u + KPE_PSF_MAXLEN)
 // Code bytes of a corpus: [capability sets | sysctls | annotation keys | annotation values], each
-// part 4-byte aligned (PsaCodes offsets). Capability set: CS_* bits (kernels.hip) | 8: the set
+// part 4-byte aligned (PsaCodes offsets). Capability set: CS_* bits (scan.hip) | 8: the set
 // holds a capability id >= 64 (never read: such a resource is a per-resource limit row); sysctl:
 // bit v = outside version v's allowed set; annotation key: bit 0 AppArmor container key, bit 1
 // pod seccomp key; annotation value: bit 0 allowed AppArmor profile, bit 1 allowed seccomp profile.

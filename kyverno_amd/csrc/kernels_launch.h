@@ -1,0 +1,63 @@
+// The host/device launch interface: every extern "C" launcher and query that the kernel sources
+// (*.hip) define and kpe_api.cpp calls, declared once. Both sides include this header, so a
+// launcher whose parameters differ from its declaration fails to compile where it is defined.
+// (The argument structs stay in kernels_abi.h, which is free of HIP types.)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "kernels_abi.h"
+
+// Scan-kernel selection: the `kind` argument of kpe_scan_grid / kpe_launch_scan / kpe_launch_prep,
+// Binding::lean_kind / gen_code and kpe_kernel_stats::scan_kernel (include/kpe.h). The numbers are
+// public (kpe_debug_lean_kind, bench.py, the tests) and do not change.
+enum KpeScanKind : int {
+  KPE_SCAN_WIDE = 0,     // kpe_scan_kernel, transposed rule pass
+  KPE_SCAN_NARROW = 1,   // kpe_scan_kernel, per-lane rule loop
+  KPE_SCAN_LEAN = 2,     // kpe_scan_kernel<PSS, NARROW, LEAN>: the LEAN template instance
+  KPE_SCAN_PSUM = 4,     // flag on WIDE / NARROW: PSS tiles read the scan records, no lists
+  KPE_SCAN_LEAN6 = 7,    // kpe_lean6_kernel (kpe_launch_lean6; sizes its own grid)
+  KPE_SCAN_BATCHED = 9,  // kpe_kernel_stats::scan_kernel only: LEAN6 over several bound shards
+};
+
+extern "C" {
+// scan.hip
+hipError_t kpe_launch_pred(const PredArgs* a, uint32_t xblocks, hipStream_t s);
+uint32_t kpe_scan_grid(int64_t n, int pss, int kind, size_t dyn_bytes);
+hipError_t kpe_launch_scan(const ScanArgs* dargs, int64_t n, int pss, int kind, uint32_t grid, size_t dyn_bytes,
+                           hipStream_t s);
+hipError_t kpe_launch_prep(const ScanArgs* dargs, int pss, int narrow, size_t dyn_bytes, hipStream_t s);
+hipError_t kpe_launch_selmask(const SelMaskArgs* a, hipStream_t s);
+hipError_t kpe_launch_lean6(const LeanBatchArgs* a, size_t dyn_bytes, int lc, hipStream_t s);
+hipError_t kpe_launch_psa_codes(const PsaCodeArgs* a, hipStream_t s);
+hipError_t kpe_launch_psum(const PsumArgs* a, hipStream_t s);
+// pattern.hip, pattern_trace.hip
+hipError_t kpe_launch_leaf_table(const PatArgs* dargs, const uint32_t* slot_leaf, uint32_t nslots, uint64_t nscal,
+                                 hipStream_t s);
+hipError_t kpe_launch_pattern(const PatArgs* dargs, int64_t n, uint32_t npr, int lt, hipStream_t s);
+hipError_t kpe_launch_pattern_trace(const PatArgs* dargs, const uint64_t* cells, uint64_t n, uint32_t* out,
+                                    const uint4* jobs, hipStream_t s);
+// cond.hip, cond_fepat.hip (kpe_launch_cond forwards to the FEPAT instance's launcher)
+hipError_t kpe_launch_cond(const CondArgs* dargs, int64_t n, int fepat, int txt, hipStream_t s);
+hipError_t kpe_launch_cond_fepat(const CondArgs* dargs, int64_t n, int txt, hipStream_t s);
+// pssx.hip
+hipError_t kpe_launch_pssx(const PssxArgs* dargs, int64_t n, hipStream_t s);
+// results.hip
+hipError_t kpe_launch_count(const uint8_t* verdicts, int64_t n, uint32_t R, unsigned long long* out, hipStream_t s);
+hipError_t kpe_launch_fill_rows(uint8_t* verdicts, uint32_t R, const uint32_t* rows, uint32_t nrows, uint8_t value,
+                                hipStream_t s);
+hipError_t kpe_launch_apply_one(uint8_t* verdicts, uint32_t* masks, int64_t n, uint32_t R, const uint32_t* segs,
+                                uint32_t nsegs, hipStream_t s);
+hipError_t kpe_launch_pack3(const uint8_t* v, uint64_t cells, uint32_t* out, hipStream_t s);
+hipError_t kpe_launch_select_count(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* sel, int na_selected,
+                                   uint32_t* tile_counts, uint64_t* tile_offs, hipStream_t s);
+hipError_t kpe_launch_select_scatter(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* sel, int na_selected,
+                                     const uint64_t* tile_offs, uint64_t cap, uint64_t* out_cells, uint8_t* out_v,
+                                     hipStream_t s);
+hipError_t kpe_launch_row_summary(const uint8_t* v, uint32_t R, uint64_t row0, uint64_t nrows, const uint8_t* unscored,
+                                  uint32_t* out, hipStream_t s);
+hipError_t kpe_launch_ns_counts(const uint8_t* v, uint32_t R, const uint32_t* rows, const KpeNsItem* items,
+                                uint64_t nitems, uint32_t g0, uint32_t* out, hipStream_t s);
+uint32_t kpe_ns_chunk_rows(void);
+}

@@ -20,6 +20,7 @@
 #include "../../include/kpe.h"
 #include "corpus.hpp"
 #include "kernels_abi.h"
+#include "kernels_launch.h"
 #include "patclass.hpp"
 #include "program.hpp"
 #include "pss_fixed.hpp"
@@ -29,42 +30,6 @@ namespace kpe {
 void flatten_ndjson(Corpus& C, const char* buf, size_t len, const char* nsl, size_t nsl_len, bool docs);
 bool is_limit_error(const std::exception& e);
 }  // namespace kpe
-
-extern "C" hipError_t kpe_launch_pred(const PredArgs* a, uint32_t nblocks, hipStream_t s);
-extern "C" hipError_t kpe_launch_pattern(const PatArgs* dargs, int64_t n, uint32_t npr, int lt, hipStream_t s);
-extern "C" hipError_t kpe_launch_pattern_trace(const PatArgs* dargs, const uint64_t* cells, uint64_t n, uint32_t* out,
-                                               const uint4* jobs, hipStream_t s);
-extern "C" hipError_t kpe_launch_cond(const CondArgs* dargs, int64_t n, int fepat, int txt, hipStream_t s);
-extern "C" hipError_t kpe_launch_fill_rows(uint8_t* verdicts, uint32_t R, const uint32_t* rows, uint32_t nrows,
-                                           uint8_t value, hipStream_t s);
-extern "C" hipError_t kpe_launch_prep(const ScanArgs* dargs, int pss, int narrow, size_t dyn_bytes, hipStream_t s);
-extern "C" hipError_t kpe_launch_pssx(const PssxArgs* dargs, int64_t n, hipStream_t s);
-extern "C" hipError_t kpe_launch_pack3(const uint8_t* v, uint64_t cells, uint32_t* out, hipStream_t s);
-extern "C" hipError_t kpe_launch_apply_one(uint8_t* verdicts, uint32_t* masks, int64_t n, uint32_t R, const uint32_t* segs,
-                                           uint32_t nsegs, hipStream_t s);
-extern "C" hipError_t kpe_launch_scan(const ScanArgs* dargs, const ScanArgs* hargs, int64_t n, int pss, int narrow,
-                                      uint32_t grid,
-                                      size_t dyn_bytes, hipStream_t s);
-extern "C" uint32_t kpe_scan_grid(int64_t n, int pss, int narrow, size_t dyn_bytes);
-extern "C" hipError_t kpe_launch_psum(const PsumArgs* a, hipStream_t s);
-extern "C" hipError_t kpe_launch_psa_codes(const PsaCodeArgs* a, hipStream_t s);
-extern "C" hipError_t kpe_launch_lean6(const LeanBatchArgs* a, size_t dyn_bytes, int lc, hipStream_t s);
-extern "C" hipError_t kpe_launch_selmask(const SelMaskArgs* a, hipStream_t s);
-extern "C" hipError_t kpe_launch_leaf_table(const PatArgs* dargs, const uint32_t* slot_leaf, uint32_t nslots,
-                                            uint64_t nscal, hipStream_t s);
-extern "C" hipError_t kpe_launch_count(const uint8_t* verdicts, int64_t n, uint32_t R, unsigned long long* out,
-                                       hipStream_t s);
-extern "C" hipError_t kpe_launch_select_count(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* sel,
-                                              int na_selected, uint32_t* tile_counts, uint64_t* tile_offs,
-                                              hipStream_t s);
-extern "C" hipError_t kpe_launch_select_scatter(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* sel,
-                                                int na_selected, const uint64_t* tile_offs, uint64_t cap,
-                                                uint64_t* out_cells, uint8_t* out_v, hipStream_t s);
-extern "C" hipError_t kpe_launch_row_summary(const uint8_t* v, uint32_t R, uint64_t row0, uint64_t nrows,
-                                             const uint8_t* unscored, uint32_t* out, hipStream_t s);
-extern "C" hipError_t kpe_launch_ns_counts(const uint8_t* v, uint32_t R, const uint32_t* rows, const KpeNsItem* items,
-                                           uint64_t nitems, uint32_t g0, uint32_t* out, hipStream_t s);
-extern "C" uint32_t kpe_ns_chunk_rows(void);
 
 namespace {
 thread_local std::string g_err;
@@ -240,8 +205,8 @@ struct Binding {  // program x corpus (dictionary sizes decide predicate placeme
   uint32_t pimg_words = 0, capb_lds = 0;
   size_t prep_dyn_bytes = 0;  // the prep kernel's LDS: the scan layout + the fuse area
   bool lean = false;  // LEAN scan instantiation (kind table; no check masks)
-  int lean_kind = 0;  // kpe_launch_scan narrow code of the LEAN scan: 7 kpe_lean6_kernel, 2 the template
-  int gen_code = 0;   // narrow code of the general scan: narrow | 4 with scan records (PSUM)
+  int lean_kind = 0;  // KpeScanKind of the LEAN scan: KPE_SCAN_LEAN6 (kpe_lean6_kernel) or KPE_SCAN_LEAN
+  int gen_code = 0;   // KpeScanKind of the general scan: WIDE / NARROW, | KPE_SCAN_PSUM with scan records
   uint32_t kt_lds = PRED_NONE, nkinds = 0;
   DevBuf xexcl, ann_norm, rf_ann, xargs;  // podSecurity exclusions: resolved excludes, key tables, PssxArgs
   bool xargs_valid = false;
@@ -444,10 +409,11 @@ static bool lean6_fits(const kpe::Corpus& C, uint64_t lim) {
   return true;
 }
 // Diagnostic (not in kpe.h): the LEAN instantiation a binding of c would pick under a column
-// limit of `lim` bytes (0: the real limit): 7 kpe_lean6_kernel, 2 the template scan.
+// limit of `lim` bytes (0: the real limit): KPE_SCAN_LEAN6 (7) kpe_lean6_kernel, KPE_SCAN_LEAN (2)
+// the template scan.
 int kpe_debug_lean_kind(const kpe_corpus* c, uint64_t lim) {
   if (!c) return -KPE_E_INVALID;
-  return lean6_fits(*c->c, lim ? lim : kLean6Limit) ? 7 : 2;
+  return lean6_fits(*c->c, lim ? lim : kLean6Limit) ? KPE_SCAN_LEAN6 : KPE_SCAN_LEAN;
 }
 
 kpe_status kpe_corpus_row_flags(const kpe_corpus* c, uint32_t* out) {
@@ -1432,13 +1398,13 @@ kpe_status ensure_binding(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc
   B.nblocks = blk;
   // LEAN evaluations run kpe_lean6_kernel (buffer loads with 32-bit byte offsets: every column it
   // reads under 4 GiB), else the template instantiation (64-bit pointers)
-  B.lean_kind = !lean ? 0 : lean6_fits(C, kLean6Limit) ? 7 : 2;
+  B.lean_kind = !lean ? 0 : lean6_fits(C, kLean6Limit) ? KPE_SCAN_LEAN6 : KPE_SCAN_LEAN;
   // the PSA dictionary codes of the corpus (policy-independent; per distinct string)
   if (P.any_pss && !cc->d->codes_ready)
     if (kpe_status st = run_codes(C, *cc->d, s)) return st;
-  // the general scan of a podSecurity program reads per-pod PSA records (PSUM instantiation, code
-  // | 4) that kpe_psum_kernel rebuilds before it every time, or (KPE_PSUM=0) walks the pods' lists
-  B.gen_code = (narrow ? 1 : 0) | (P.any_pss && !dev->no_psum ? 4 : 0);
+  // the general scan of a podSecurity program reads per-pod PSA records (PSUM instantiation) that
+  // kpe_psum_kernel rebuilds before it every time, or (KPE_PSUM=0) walks the pods' lists
+  B.gen_code = (narrow ? KPE_SCAN_NARROW : KPE_SCAN_WIDE) | (P.any_pss && !dev->no_psum ? KPE_SCAN_PSUM : 0);
   B.scan_blocks = kpe_scan_grid(C.n, P.any_pss ? 1 : 0, lean ? B.lean_kind : B.gen_code, B.dyn_bytes);
   HIPCHK(upload(B.jobs, jobs, s));
   {  // ApplyOne policies: contiguous rule ranges in ComputeRules order
@@ -1502,8 +1468,8 @@ kpe_status launch(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc, bool m
   const bool fresh = !B.inv_ready || dev->no_cache || cold;
   if (cold && P.any_pss)  // a cold evaluation rebuilds the corpus's PSA dictionary codes too
     if (kpe_status st = run_codes(C, D, s)) return st;
-  const bool lean_go = B.lean && (!masks || B.lean_kind == 7);  // LEAN6 writes check masks too
-  const bool six = lean_go && B.lean_kind == 7;
+  const bool lean_go = B.lean && (!masks || B.lean_kind == KPE_SCAN_LEAN6);  // LEAN6 writes check masks too
+  const bool six = lean_go && B.lean_kind == KPE_SCAN_LEAN6;
   const bool psum_go = P.any_pss && !lean_go && !dev->no_psum;  // the PSUM scan and its per-pod records
   if (psum_go) HIPCHK(D.psum.ensure((size_t)C.n * 12 + 16));
   if (B.nblocks && fresh) {  // dictionary pass for large-domain predicates
@@ -1653,7 +1619,7 @@ kpe_status launch(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc, bool m
     // the general scan of a podSecurity program reads per-pod PSA records built right here
     if (psum_go)
       if (kpe_status st = run_psum(C, D, s)) return st;
-    HIPCHK(kpe_launch_scan(B.dargs.as<ScanArgs>(), &B.hargs, C.n, P.any_pss ? 1 : 0, lean_go ? B.lean_kind : B.gen_code,
+    HIPCHK(kpe_launch_scan(B.dargs.as<ScanArgs>(), C.n, P.any_pss ? 1 : 0, lean_go ? B.lean_kind : B.gen_code,
                            B.scan_blocks, B.dyn_bytes, s));
   }
   if (dev->timing) HIPCHK(hipEventRecord(ev.c, s));
@@ -1840,7 +1806,7 @@ kpe_status launch(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc, bool m
     const bool ps = psum_go;
     ev.bytes = six ? lbytes : scan_bytes(P, C, B.need, masks, ps) + (ps ? psum_bytes(C, D, B.need) : 0.0);
     ev.pbytes = P.pat.rules.empty() ? 0.0 : (double)C.doc.size() * 4.0 + (double)C.n * (8.0 + 2.0 * (double)R);
-    ev.kind = lean_go ? B.lean_kind : 1;
+    ev.kind = lean_go ? B.lean_kind : 1;  // 1: the general scan, whichever instance (kpe.h)
     dev->pending.push_back(ev);
   }
   return KPE_OK;
@@ -1909,9 +1875,9 @@ bool lean_batchable(const kpe_device* dev, const kpe_program* pp, const kpe_corp
   const auto& C = *cc->c;
   const auto& D = *cc->d;
   const auto& B = D.bind;
-  return !dev->no_cache && B.prog == &P && B.inv_ready && B.lean && B.lean_kind == 7 && D.codes_ready && C.n > 0 &&
-         B.nkinds <= kLeanBatchKinds && P.cond.rules.empty() && P.pssx.rules.empty() && P.pat.rules.empty() &&
-         !B.napply_segs && C.limit_rows.empty();
+  return !dev->no_cache && B.prog == &P && B.inv_ready && B.lean && B.lean_kind == KPE_SCAN_LEAN6 &&
+         D.codes_ready && C.n > 0 && B.nkinds <= kLeanBatchKinds && P.cond.rules.empty() && P.pssx.rules.empty() &&
+         P.pat.rules.empty() && !B.napply_segs && C.limit_rows.empty();
 }
 
 // The shards of `run` in ceil(m / KPE_LEAN_BATCH) launches of near-equal size on the device
@@ -1946,7 +1912,7 @@ kpe_status launch_lean_run(kpe_device* dev, const kpe_program* pp, std::vector<k
     if (dev->timing) {
       HIPCHK(hipEventRecord(ev.c, s));
       HIPCHK(hipEventRecord(ev.d, s));
-      ev.bytes = bytes, ev.pbytes = 0, ev.kind = 9, ev.pre = ev.post = false;
+      ev.bytes = bytes, ev.pbytes = 0, ev.kind = KPE_SCAN_BATCHED, ev.pre = ev.post = false;
       dev->pending.push_back(ev);
     }
   }

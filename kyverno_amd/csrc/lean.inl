@@ -9,7 +9,7 @@
 // belong to the corpus's dictionaries (one byte per distinct capability set, sysctl name and
 // annotation key / value: kpe_psa_codes_kernel, once per corpus, like the interned ids
 // themselves); everything per pod is read and decided by every evaluation (kpe_lean6_kernel).
-// Included by kernels.hip (uses its anonymous-namespace helpers).
+// Included by scan.hip (uses its anonymous-namespace helpers).
 
 typedef __amdgpu_buffer_rsrc_t Rsrc;
 __device__ __forceinline__ Rsrc make_rsrc(const void* p, uint32_t bytes) {

@@ -1,6 +1,6 @@
-// Pattern VM: validate.MatchPattern over the document tape (see kernels.hip). Device code
-// included inside kernels.hip's anonymous namespace; scripts/patvm_check.cpp compiles the
-// same text for the host (sanitizers, no GPU).
+// Pattern VM: validate.MatchPattern over the document tape (see pattern.hip). Device code
+// included inside an anonymous namespace by pattern.hip, pattern_trace.hip and cond_kernel.inl;
+// scripts/patvm_check.cpp compiles the same text for the host (sanitizers, no GPU).
 constexpr uint32_t PE_OK = 0, PE_SKIP = 1, PE_NEG = 2, PE_OTHER = 3, PE_OTHER_NOPATH = 4, PE_PUSHED = 8,
                    PE_NONE = 9;
 constexpr uint32_t kNoNode = 0xFFFFFFFFu;

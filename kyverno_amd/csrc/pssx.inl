@@ -1,5 +1,5 @@
 // podSecurity.exclude on the device: kpe_pssx_kernel's per-pod body. Included inside
-// kernels.hip's anonymous namespace.
+// pssx.hip's anonymous namespace.
 //
 // Restates pkg/pss/evaluate.go for rules with exclusions:
 //   EvaluatePod :242-252, ApplyPodSecurityExclusion :255-279, GetPodWithMatchingContainers

@@ -1,4 +1,4 @@
-// CDNA4 (gfx950) kernels for batch policy evaluation. wave64, HBM-bound scans.
+// CDNA4 (gfx950) scan-side kernels for batch policy evaluation. wave64, HBM-bound scans.
 //
 //  kpe_pred_kernel   — dictionary pass: every string predicate of the compiled
 //                      program (an OR of go-wildcard globs, ext/wildcard/match.go:7-9)
@@ -17,44 +17,17 @@
 //                      exclude pkg/engine/utils/match.go:168-300, ApplyOne
 //                      pkg/engine/validation.go:75-77; (4) verdict cells staged per wave
 //                      in LDS and stored as contiguous row segments.
-//  kpe_count_kernel  — per-rule status histogram of a verdict matrix (the CLI totals
-//                      of cmd/cli/kubectl-kyverno/processor/result.go:34-68); fetch time.
-#include <hip/hip_runtime.h>
-#include <cstdlib>
-#include <stdint.h>
+//  lean.inl          — kpe_lean6_kernel (the LEAN evaluation), kpe_psa_codes_kernel,
+//                      kpe_psum_kernel (the general scan's per-pod PSA records).
+//  kpe_selmask_kernel — selector requirement masks, once per binding.
+// The other kernel families: results.hip (counts, selection, summaries), pattern.hip,
+// pattern_trace.hip, cond.hip / cond_fepat.hip, pssx.hip.
+#include "kernels_common.h"
 
-#include <algorithm>
-
-#include "kernels_abi.h"
-#include "schema.h"
-
-namespace {
-#include "strmatch.inl"
-
-#ifndef KPE_PSUM_LABPRE
-#define KPE_PSUM_LABPRE 0  // 1: PSUM tiles carry the label bounds and namespace row (C4 0.420 / 0.427 against
-                           // 0.415 / 0.416 ms, 6 spills; profiles/r06_l)
-#endif
-// Wave-uniform table read: the address is uniform, so this is a scalar (SMEM) load
-// through the constant cache — no LDS round trip and no readfirstlane to branch on it.
 #ifndef KPE_DIAG
 #define KPE_DIAG 0  // diagnostic builds only (scripts/diag_scan.sh): sections of the WIDE scan left out
 #endif
-template <class T>
-__device__ __forceinline__ T sld(const T* p, uint32_t i) {
-  static_assert(sizeof(T) % 4 == 0, "word-sized tables");
-  typedef __attribute__((address_space(4))) const uint32_t* cptr;
-  const cptr src = (cptr)(p + i);
-  T out;
-  uint32_t* d = reinterpret_cast<uint32_t*>(&out);
-#pragma unroll
-  for (uint32_t k = 0; k < sizeof(T) / 4; ++k) d[k] = src[k];
-  return out;
-}
 
-}  // namespace
-
-#ifndef KPE_VM_ONLY
 // ---------------------------------------------------------------------------
 constexpr uint32_t kPredStrLds = 16384;  // staged dictionary bytes per block
 constexpr uint32_t kPredPatLds = 4096;   // staged pattern bytes
@@ -104,35 +77,11 @@ __global__ void __launch_bounds__(256) kpe_pred_kernel(PredArgs a) {
     a.out[job.out_word + 2 * wid + 1] = (uint32_t)(m >> 32);
   }
 }
-
-// Per-rule status histogram of a row-major N x R verdict matrix (8 slots per rule: the
-// kpe_verdict codes). Each wave takes 64 rows at a time; per rule, one ballot per status,
-// lane 0 accumulates in LDS; one 64-bit global add per (rule, status) and block at the end.
-__global__ void __launch_bounds__(256) kpe_count_kernel(const uint8_t* v, int64_t n, uint32_t R, uint32_t r0,
-                                                        uint32_t rn, unsigned long long* out) {
-  extern __shared__ uint32_t hist[];  // rules [r0, r0 + rn) x 8
-  const uint32_t t = threadIdx.x, lane = t & 63u;
-  for (uint32_t i = t; i < rn * 8; i += 256) hist[i] = 0;
-  __syncthreads();
-  const int64_t nw = (int64_t)gridDim.x * 4;
-  for (int64_t tile = (int64_t)blockIdx.x * 4 + (t >> 6); tile * 64 < n; tile += nw) {
-    const int64_t row = tile * 64 + lane;
-    const bool live = row < n;
-    for (uint32_t r = 0; r < rn; ++r) {
-      const uint32_t c = live ? v[row * R + r0 + r] : 0u;
-#pragma unroll
-      for (uint32_t s = 1; s < 8; ++s) {
-        const uint32_t k = (uint32_t)__popcll(__ballot(c == s));
-        if (lane == 0 && k) atomicAdd(&hist[r * 8 + s], k);
-      }
-    }
-  }
-  __syncthreads();
-  for (uint32_t i = t; i < rn * 8; i += 256)
-    if (hist[i]) atomicAdd(&out[(size_t)r0 * 8 + i], (unsigned long long)hist[i]);
+extern "C" hipError_t kpe_launch_pred(const PredArgs* a, uint32_t xblocks, hipStream_t s) {
+  if (xblocks == 0 || a->njobs == 0) return hipSuccess;
+  hipLaunchKernelGGL(kpe_pred_kernel, dim3(xblocks, a->njobs), dim3(256), 0, s, *a);
+  return hipGetLastError();
 }
-
-#endif  // !KPE_VM_ONLY
 
 // ---------------------------------------------------------------------------
 namespace {
@@ -196,18 +145,6 @@ __device__ __forceinline__ uint32_t cv_fails(uint32_t pw, uint32_t xo, uint32_t 
   f |= on(sys_bad & 1u, CV_SYSCTLS_1_0) | on(sys_bad & 2u, CV_SYSCTLS_1_27) | on(sys_bad & 4u, CV_SYSCTLS_1_29);
   f |= on((uint32_t)(FIELD(pw, P_WHP_SH, 2) == TRI_TRUE) | (uint32_t)((xo & CX_WHP_T) != 0u), CV_WIN_HOST_PROCESS_1_0);
   return f;
-}
-
-// Inclusive wave64 prefix sum: 4 row_shr steps inside each 16-lane row, then
-// row_bcast:15 / row_bcast:31 across rows (6 DPP adds, no LDS).
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x111, 0xf, 0xf, false);
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x112, 0xf, 0xf, false);
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x114, 0xf, 0xf, false);
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x118, 0xf, 0xf, false);
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x142, 0xa, 0xf, false);
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x143, 0xc, 0xf, false);
-  return x;
 }
 
 // The scan's arguments live in device memory (one copy per program x corpus
@@ -333,14 +270,6 @@ __device__ __forceinline__ Tile<true> load_pss_tile(CArgs& a, uint32_t tile, uin
     const bool on_n = need & NEED_NAME, on_m = need & NEED_MNS;
     d.name = col<uint32_t>(on_n, a.r_name, zp)[on_n ? rc : 0u];
     d.mns = col<uint32_t>(on_m, a.r_mns, zp)[on_m ? rc : 0u];
-#if KPE_PSUM_LABPRE
-    // the list slots the records replace carry the label bounds and the namespace row one step
-    // ahead of the label loads (lab_cache)
-    const bool on_l = need & NEED_LAB, on_s = need & NEED_NSL;
-    const uint32_t* lo = col<uint32_t>(on_l, a.lab_off, zp) + (on_l ? rc : 0u);
-    d.v0 = lo[0], d.v1 = lo[on_l ? 1u : 0u];
-    d.s0 = col<uint32_t>(on_s, a.r_nsl, zp)[on_s ? rc : 0u];
-#endif
     return d;
   }
   const bool on_c = a.nctr_total, on_sa = on_c && (need & NEED_SANN);
@@ -605,7 +534,7 @@ __device__ __forceinline__ uint64_t sel_fold(CArgs& a, const LabCache& LC, const
 }
 
 // lo / hi / nsl: the resource's lab_off bounds and r_nsl row when the tile prefetched them
-// (Tile<false>, or PSUM tiles' list slots), else kNotFetched
+// (Tile<false>), else kNotFetched
 constexpr uint32_t kNotFetched = 0xFFFFFFFEu;  // r_nsl rows and label offsets stay below it
 __device__ __forceinline__ void lab_cache(CArgs& a, uint32_t rc, bool live, LabCache& LC, const uint32_t* dyn,
                                           uint32_t lo = kNotFetched, uint32_t hi = 0u, uint32_t nsl = kNotFetched) {
@@ -1028,8 +957,7 @@ __global__ void __launch_bounds__(kBlock, LEAN ? KPE_LEAN_WAVES : KPE_SCAN_WAVES
       uint32_t tb = 0;
       if constexpr (!LEAN) {
         LabCache LC;
-        if constexpr (PSS && PSUM && KPE_PSUM_LABPRE) lab_cache(a, rc, live, LC, dyn, cur.v0, cur.v1, cur.s0);
-        else if constexpr (PSS) lab_cache(a, rc, live, LC, dyn);
+        if constexpr (PSS) lab_cache(a, rc, live, LC, dyn);
         else lab_cache(a, rc, live, LC, dyn, cur.lo, cur.hi, cur.nsl);
         if (a.kslot_lds != PRED_NONE) LC.kmask = kslot_mask(a, dyn, gvk);
 #pragma unroll 1
@@ -1055,16 +983,6 @@ __global__ void __launch_bounds__(kBlock, LEAN ? KPE_LEAN_WAVES : KPE_SCAN_WAVES
       }
       // ---- rules, in program order, for this lane's resource ----
       bool applied = false;
-#ifdef KPE_NARROW_FV
-      // every filter once per lane into a bit vector (a filter holds when all of its terms hold);
-      // a block is then one mask test over its filters [f0, f0 + nf)
-      uint64_t fv = 0;
-#pragma unroll 1
-      for (uint32_t f = 0; f < a.nfilters; ++f) {
-        const uint32_t fm = hw(fm_lane, f);
-        fv |= (uint64_t)((tb & fm) == fm) << f;
-      }
-#endif
 #pragma unroll 1
       for (uint32_t ri = 0; ri < R; ++ri) {
         const uint4 nr = make_uint4(hw(myrule.x, ri), hw(myrule.y, ri), hw(myrule.z, ri), hw(myrule.w, ri));
@@ -1072,10 +990,6 @@ __global__ void __launch_bounds__(kBlock, LEAN ? KPE_LEAN_WAVES : KPE_SCAN_WAVES
         // a block is an OR (any / legacy) or AND (all) of filters; a filter holds when
         // all of its terms hold: (tb & mask) == mask
         auto block = [&](uint32_t mode, uint32_t f0, uint32_t nf) -> bool {
-#ifdef KPE_NARROW_FV
-          const uint64_t M = (nf >= 64u ? ~0ull : ((1ull << nf) - 1ull)) << f0;
-          return mode == MODE_ALL ? (fv & M) == M : (fv & M) != 0ull;
-#else
           const bool all = mode == MODE_ALL;
           bool acc = all;
 #pragma unroll 1
@@ -1085,10 +999,9 @@ __global__ void __launch_bounds__(kBlock, LEAN ? KPE_LEAN_WAVES : KPE_SCAN_WAVES
             acc = all ? (acc && h) : (acc || h);
           }
           return acc;
-#endif
         };
         const uint32_t pol = NR_POLTERM(x);
-        bool m = live && (pol == 0u || ((tb >> (pol - 1u)) & 1u));
+        bool m = live &&(pol == 0u || ((tb >> (pol - 1u)) & 1u));
         m = m && block(NR_MATCH_MODE(x), RL_F0(nr.z), RL_NF(nr.z));
         m = m && !block(NR_EXCL_MODE(x), RL_F0(nr.w), RL_NF(nr.w));
         const uint32_t hd = NR_HANDLER(x);
@@ -1122,8 +1035,7 @@ __global__ void __launch_bounds__(kBlock, LEAN ? KPE_LEAN_WAVES : KPE_SCAN_WAVES
         a.filt_lds != PRED_NONE ? reinterpret_cast<const KpeFilter*>(dyn + a.filt_lds) : a.filters;
     const uint32_t* fterm = a.filt_lds != PRED_NONE ? dyn + a.fterm_lds : a.fterms;
     LabCache LC;
-    if constexpr (PSS && PSUM && KPE_PSUM_LABPRE) lab_cache(a, rc, live, LC, dyn, cur.v0, cur.v1, cur.s0);
-    else if constexpr (PSS) lab_cache(a, rc, live, LC, dyn);
+    if constexpr (PSS) lab_cache(a, rc, live, LC, dyn);
     else lab_cache(a, rc, live, LC, dyn, cur.lo, cur.hi, cur.nsl);
     if (a.kslot_lds != PRED_NONE) LC.kmask = kslot_mask(a, dyn, gvk);
 #if KPE_DIAG & 2  // diagnostic build: no term evaluation
@@ -1284,270 +1196,18 @@ __global__ void __launch_bounds__(kBlock, LEAN ? KPE_LEAN_WAVES : KPE_SCAN_WAVES
   }
 }
 
-
-#ifndef KPE_VM_ONLY
 #include "lean.inl"
-#endif
-
-// ---------------------------------------------------------------------------
-// Host-side launch wrappers (called from kpe_api.cpp).
-// grid: x = blocks of the largest job, y = jobs
-// ===========================================================================
-// Pattern rules: validate.MatchPattern over the document tape
-// (pkg/engine/validate/validate.go:15-261, anchor/handlers.go:31-275, pattern/pattern.go).
-// One lane per resource runs the compiled pattern (program.cpp pc::PatCompiler) against
-// its document nodes; cells the scan kernel marked KPE_PENDING_ (rule matched) are
-// resolved to pass / fail / error / skip. Only the class of the error a subtree returns
-// and whether its path is empty decide the verdict, so that is all a subtree reports.
-// The reference's recursion is an explicit per-lane frame stack (no calls, so no spilled
-// call frames and no callee register budget): a frame is a map validated member by
-// member, or an array validated element by element; scalar leaves resolve in place.
-// ===========================================================================
-namespace {
-#include "patvm.inl"
-}  // namespace
-
-#ifndef KPE_SCAN_ONLY
-// The VM side builds as three objects in parallel (KPE_VM_PART 1: pattern kernels, 2: condition
-// kernel without the pattern VM, pssx, pack3, traces; 3: the condition kernel with it); undefined:
-// all of them in one object.
-#ifndef KPE_VM_PART
-#define KPE_VM_PART 0
-#endif
-#define KPE_IN_PART(p) (KPE_VM_PART == 0 || KPE_VM_PART == (p))
-// grid: 256-row blocks, one lane per row running every pattern rule
-#ifndef KPE_PAT_BLOCK
-#define KPE_PAT_BLOCK 128  // C5 / C3 pattern kernel (events, profiles/r03_c_ldsframes): 256 x 8 frames 20.7 / 9.2 ms,
-#endif                     // 128 x 8 18.1 / 7.8, 256 x 6 17.2 / 7.0, 128 x 6 16.8 / 6.9, + 4 waves/SIMD 15.6 / 7.0
-// the lane's frame stack lives in LDS (FramesLds, word-planar: conflict-free at any mix of depths)
-#ifndef KPE_PAT_MINW
-#define KPE_PAT_MINW 3  // the leaf-table instance takes 111 VGPRs (4 waves/SIMD, as many as the 8 LDS-bound
-                        // blocks per CU hold), the one without 166; the inline map path spills at 128 (r03_e_inline)
-#endif
-#if KPE_IN_PART(1)
-// LT: the leaf-table instance (PatVMT LT), for programs whose leaves all have table slots.
-template <bool LT>
-__global__ void __launch_bounds__(KPE_PAT_BLOCK, KPE_PAT_MINW) kpe_pattern_kernel(const PatArgs* __restrict__ ap) {
-  constexpr uint32_t kWaveWords = FramesLds::kWords * FramesLds::kDepth * 64u;
-  __shared__ uint32_t s_fs[KPE_PAT_BLOCK / 64][kWaveWords];
-  __shared__ uint8_t s_memo[KPE_PAT_MEMO][KPE_PAT_BLOCK];  // byte-planar: a lane's slot s at [s][lane]
-  const int64_t i = (int64_t)blockIdx.x * KPE_PAT_BLOCK + threadIdx.x;
-  if (i >= ap->n) return;
-  const int64_t r = ap->perm ? (int64_t)ap->perm[i] : i;
-  pat_eval_row<FramesLds, LT, true>(*ap, r, FramesLds{&s_fs[threadIdx.x >> 6][threadIdx.x & 63u]},
-                                    &s_memo[0][threadIdx.x], KPE_PAT_BLOCK);
-}
-// The cells kpe_pattern_kernel marked KPE_DEEP_ (one lane per row; rows without marks only scan),
-// on a kPatStack-deep LDS frame stack (one-wave blocks: 25 KiB of LDS each).
-template <bool LT>
-__global__ void __launch_bounds__(64) kpe_pattern_deep_kernel(const PatArgs* __restrict__ ap) {
-  __shared__ uint32_t s_fs[FramesLdsDeep::kWords * FramesLdsDeep::kDepth * 64u];
-  if (ap->deep_any && *ap->deep_any == 0u) return;  // kpe_pattern_kernel marked no cell
-  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (i >= ap->n) return;
-  // rows through doc_perm (grouped by kind, then tape size) like the main kernel: the rows with deep
-  // cells (one kind's deeper autogen patterns) fill whole waves instead of a few lanes of each
-  const int64_t r = ap->perm ? (int64_t)ap->perm[i] : i;
-  pat_deep_row<LT>(*ap, r, FramesLdsDeep{&s_fs[threadIdx.x]});
-}
-
-// Leaf table of a binding (PatArgs::ltab): grid y = slot, one thread per scalar of the corpus;
-// a wave's 64 results are one ballot, stored as two words (ltab_words covers whole waves).
-__global__ void __launch_bounds__(256) kpe_leaf_table_kernel(const PatArgs* __restrict__ ap,
-                                                             const uint32_t* __restrict__ slot_leaf) {
-  const PatArgs& a = *ap;
-  const uint32_t sid = blockIdx.x * 256u + threadIdx.x, slot = blockIdx.y;
-  uint32_t und = 0;
-  const bool r = sid < a.nscal && pat_leaf_eval(a, sid, slot_leaf[slot], nullptr, &und);
-  const uint64_t m = __ballot(r);
-  if ((threadIdx.x & 63u) == 0u && sid < a.nscal) {
-    uint32_t* w = a.ltab + (size_t)slot * a.ltab_words + (sid >> 5);
-    w[0] = (uint32_t)m;
-    w[1] = (uint32_t)(m >> 32);
-  }
-}
-extern "C" hipError_t kpe_launch_leaf_table(const PatArgs* dargs, const uint32_t* slot_leaf, uint32_t nslots,
-                                            uint64_t nscal, hipStream_t s) {
-  if (nslots == 0 || nscal == 0) return hipSuccess;
-  hipLaunchKernelGGL(kpe_leaf_table_kernel, dim3((unsigned)((nscal + 255) / 256), nslots), dim3(256), 0, s, dargs,
-                     slot_leaf);
-  return hipGetLastError();
-}
-#endif  // KPE_IN_PART(1)
-
-// ===========================================================================
-// Preconditions / deny / foreach-deny conditions (condvm.inl): one lane per resource resolves
-// the cells of the rules whose conditions read the resource. Runs after the scan kernel (which
-// marks H_COND cells pending and writes every other handler's verdict) and before the pattern
-// kernel (a pattern cell whose preconditions hold stays pending).
-// ===========================================================================
-namespace {
-#include "condvm.inl"
-}  // namespace
-
-// FEPAT: the instance that also holds the pattern VM, for programs with foreach pattern /
-// anyPattern entries (the VM's frame stack and code stay out of the plain instance)
-// Programs with partial-string variables (VT_TMPL) get 2 x KPE_TXT_CAP bytes of dynamic LDS per
-// lane for the substituted key / value strings; the others launch without it.
-template <bool FEPAT>
-__global__ void __launch_bounds__(128) kpe_cond_kernel(const CondArgs* __restrict__ ap) {
-  __shared__ char nb[128][2][16];
-  extern __shared__ __attribute__((aligned(16))) uint8_t ctx[];
-  const int64_t i = (int64_t)blockIdx.x * 128 + threadIdx.x;
-  uint8_t* tx = ap->txt ? ctx + threadIdx.x * (2u * KPE_TXT_CAP) : nullptr;
-  if (i < ap->n) cond_eval_row<FEPAT>(*ap, ap->perm ? (int64_t)ap->perm[i] : i, nb[threadIdx.x], tx);
-}
-
-#if KPE_IN_PART(3)
-extern "C" hipError_t kpe_launch_cond_fepat(const CondArgs* dargs, int64_t n, int txt, hipStream_t s) {
-  const size_t lds = txt ? 128u * 2u * KPE_TXT_CAP : 0u;
-  hipLaunchKernelGGL(kpe_cond_kernel<true>, dim3((unsigned)((n + 127) / 128)), dim3(128), lds, s, dargs);
-  return hipGetLastError();
-}
-#endif
-
-#if KPE_IN_PART(2)
-extern "C" hipError_t kpe_launch_cond_fepat(const CondArgs* dargs, int64_t n, int txt, hipStream_t s);
-extern "C" hipError_t kpe_launch_cond(const CondArgs* dargs, int64_t n, int fepat, int txt, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  if (fepat) return kpe_launch_cond_fepat(dargs, n, txt, s);
-  const size_t lds = txt ? 128u * 2u * KPE_TXT_CAP : 0u;
-  hipLaunchKernelGGL(kpe_cond_kernel<false>, dim3((unsigned)((n + 127) / 128)), dim3(128), lds, s, dargs);
-  return hipGetLastError();
-}
-
-// ===========================================================================
-// podSecurity.exclude (pssx.inl): one lane per pod re-evaluates the failing cells of the
-// rules with exclusions. Runs after the condition kernel (preconditions may have skipped a
-// cell); reads the corpus's pod columns and the predicate bitsets in pbuf.
-// ===========================================================================
-namespace {
-#include "pssx.inl"
-}  // namespace
-
-__global__ void __launch_bounds__(128) kpe_pssx_kernel(const PssxArgs* __restrict__ ap) {
-  const int64_t r = (int64_t)blockIdx.x * 128 + threadIdx.x;
-  if (r < ap->n) pssx_eval_row(*ap, r);
-}
-
-// Verdict exchange (kpe_pack_verdicts): 3-bit cells, 10 per 32-bit word, row-major. One thread
-// per output word; neighbouring threads read neighbouring 10-byte runs (HBM-bound).
-__global__ void __launch_bounds__(256) kpe_pack3_kernel(const uint8_t* __restrict__ v, uint64_t cells,
-                                                        uint32_t* __restrict__ out, uint64_t words) {
-  const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (w >= words) return;
-  const uint64_t c0 = w * 10u;
-  uint32_t x = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < 10u; ++k)
-    if (c0 + k < cells) x |= (uint32_t)(v[c0 + k] & 7u) << (3u * k);
-  out[w] = x;
-}
-extern "C" hipError_t kpe_launch_pack3(const uint8_t* v, uint64_t cells, uint32_t* out, hipStream_t s) {
-  const uint64_t words = (cells + 9u) / 10u;
-  if (!words) return hipSuccess;
-  hipLaunchKernelGGL(kpe_pack3_kernel, dim3((unsigned)((words + 255u) / 256u)), dim3(256), 0, s, v, cells, out, words);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t kpe_launch_pssx(const PssxArgs* dargs, int64_t n, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(kpe_pssx_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, dargs);
-  return hipGetLastError();
-}
-
-// Failing paths of listed pattern cells (kpe_pattern_traces): one lane per cell (row * R + col)
-// walks each root of the cell's rule (at most KPE_TRACE_ROOTS) from the tape in HBM with the
-// VM's TRACE instance, which records the path of the last failure (PatternError.Path). A cell
-// with a job (jobs[i].w != 0: a validate.foreach cell that a pattern entry decided) walks the
-// entry's roots [x, x + y & 0xFFFF) (PR_* flags in y >> 16) from the element node z (kNoNode: the
-// resource root) instead. Report time only; the evaluation kernels never carry the tracing code.
-__global__ void __launch_bounds__(128) kpe_pattern_trace_kernel(const PatArgs* __restrict__ ap,
-                                                                 const uint64_t* __restrict__ cells, uint64_t n,
-                                                                 uint32_t* __restrict__ out,
-                                                                 const uint4* __restrict__ jobs) {
-  const uint64_t i = (uint64_t)blockIdx.x * 128u + threadIdx.x;
-  if (i >= n) return;
-  const PatArgs& a = *ap;
-  uint32_t* rec = out + i * (KPE_TRACE_ROOTS * KPE_TRACE_WORDS);
-  for (uint32_t k = 0; k < KPE_TRACE_ROOTS * KPE_TRACE_WORDS; ++k) rec[k] = 0u;
-  const uint64_t cell = cells[i];
-  const uint64_t row = cell / a.R;
-  const uint32_t col = (uint32_t)(cell - row * a.R);
-  if (row >= (uint64_t)a.n) return;
-  const uint4 job = jobs ? jobs[i] : make_uint4(0u, 0u, 0u, 0u);
-  KpePatRule pr;
-  uint32_t start = (uint32_t)a.doc_off[row];
-  if (job.w) {
-    pr.r0 = job.x, pr.nr = job.y & 0xFFFFu, pr.flags = job.y >> 16;
-    if (job.z != kNoNode) start = job.z;
-  } else {
-    if (!a.col2pr || C2P_RULE(a.col2pr[col]) == 0u) return;
-    pr = a.rules[C2P_RULE(a.col2pr[col]) - 1u];
-  }
-  PatVM vm{a, PV_DOCVIEW(a, reinterpret_cast<const uint2*>(a.doc), 0u, a.ndoc), start,
-           a.pvals + (size_t)row * a.nvars, 0u};
-  if (pr.flags & PR_ANY_BAD) {
-    rec[0] = KPE_TR_VALID | ((uint32_t)KPE_ERROR_ << 16);
-    return;
-  }
-  for (uint32_t k = 0; k < pr.nr && k < KPE_TRACE_ROOTS; ++k) {
-    vm.tr = rec + k * KPE_TRACE_WORDS;
-    const uint32_t v = pat_match_root<true>(vm, pr.r0 + k);
-    vm.tr[0] = (vm.tr[0] & 0xFFFFu) | (v << 16) | KPE_TR_VALID;
-  }
-}
-
-extern "C" hipError_t kpe_launch_pattern_trace(const PatArgs* dargs, const uint64_t* cells, uint64_t n, uint32_t* out,
-                                               const uint4* jobs, hipStream_t s) {
-  if (!n) return hipSuccess;
-  hipLaunchKernelGGL(kpe_pattern_trace_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, dargs, cells, n, out,
-                     jobs);
-  return hipGetLastError();
-}
-
-#endif  // KPE_IN_PART(2)
-
-#if KPE_IN_PART(1)
-extern "C" hipError_t kpe_launch_pattern(const PatArgs* dargs, int64_t n, uint32_t npr, int lt, hipStream_t s) {
-  if (n <= 0 || npr == 0) return hipSuccess;
-  // one lane per row running every pattern rule (a rows x rules grid measured no faster on C5 and
-  // slower on C3's 600 rules; it also doubled the VM code the kernel holds)
-  // (two or four lanes per row, each taking every 2nd / 4th pattern cell: C5 12.3 / 19.3 ms against
-  // 8.5, profiles/r04_i: the lanes of a wave then walk different rules; verdicts of a 64-column
-  // chunk written back once as whole words: C5 8.6 / C3 3.66 ms against 8.5 / 3.34, more spills,
-  // profiles/r04_j)
-  const dim3 grid((unsigned)((n + KPE_PAT_BLOCK - 1) / KPE_PAT_BLOCK));
-  const dim3 rows((unsigned)((n + 63) / 64));
-  if (lt) {
-    hipLaunchKernelGGL(kpe_pattern_kernel<true>, grid, dim3(KPE_PAT_BLOCK), 0, s, dargs);
-    hipLaunchKernelGGL(kpe_pattern_deep_kernel<true>, rows, dim3(64), 0, s, dargs);
-  } else {
-    hipLaunchKernelGGL(kpe_pattern_kernel<false>, grid, dim3(KPE_PAT_BLOCK), 0, s, dargs);
-    hipLaunchKernelGGL(kpe_pattern_deep_kernel<false>, rows, dim3(64), 0, s, dargs);
-  }
-  return hipGetLastError();
-}
-#endif  // KPE_IN_PART(1)
-
-#endif  // !KPE_SCAN_ONLY
-
-#ifndef KPE_VM_ONLY
-extern "C" hipError_t kpe_launch_pred(const PredArgs* a, uint32_t xblocks, hipStream_t s) {
-  if (xblocks == 0 || a->njobs == 0) return hipSuccess;
-  hipLaunchKernelGGL(kpe_pred_kernel, dim3(xblocks, a->njobs), dim3(256), 0, s, *a);
-  return hipGetLastError();
-}
 
 namespace {
 typedef void (*ScanFn)(const ScanArgs*);
-// narrow codes: 0 wide, 1 narrow, 2 the LEAN instantiation, | 4: PSUM (scan records, no lists)
-ScanFn scan_fn(int pss, int narrow) {
-  if (pss && narrow == 2) return kpe_scan_kernel<true, true, false, true>;
-  if (pss && (narrow & 4))
-    return (narrow & 1) ? kpe_scan_kernel<true, true, false, false, true> : kpe_scan_kernel<true, false, false, false, true>;
-  if (pss) return narrow ? kpe_scan_kernel<true, true, false> : kpe_scan_kernel<true, false, false>;
-  return narrow ? kpe_scan_kernel<false, true, false> : kpe_scan_kernel<false, false, false>;
+// kind: a KpeScanKind of the template (not KPE_SCAN_LEAN6, which is kpe_lean6_kernel)
+ScanFn scan_fn(int pss, int kind) {
+  if (pss && kind == KPE_SCAN_LEAN) return kpe_scan_kernel<true, true, false, true>;
+  if (pss && (kind & KPE_SCAN_PSUM))
+    return (kind & KPE_SCAN_NARROW) ? kpe_scan_kernel<true, true, false, false, true>
+                                    : kpe_scan_kernel<true, false, false, false, true>;
+  if (pss) return kind != KPE_SCAN_WIDE ? kpe_scan_kernel<true, true, false> : kpe_scan_kernel<true, false, false>;
+  return kind != KPE_SCAN_WIDE ? kpe_scan_kernel<false, true, false> : kpe_scan_kernel<false, false, false>;
 }
 ScanFn prep_fn(int pss, int narrow) {
   if (pss) return narrow ? kpe_scan_kernel<true, true, true> : kpe_scan_kernel<true, false, true>;
@@ -1557,8 +1217,8 @@ ScanFn prep_fn(int pss, int narrow) {
 
 // Scan grid: persistent, as many blocks as can be resident at once (occupancy x CUs), capped by
 // the number of 256-resource tiles. (The LEAN evaluation, kpe_lean6_kernel, sizes its own grid.)
-extern "C" uint32_t kpe_scan_grid(int64_t n, int pss, int narrow, size_t dyn_bytes) {
-  if (n <= 0 || (pss && narrow == 7)) return 0;
+extern "C" uint32_t kpe_scan_grid(int64_t n, int pss, int kind, size_t dyn_bytes) {
+  if (n <= 0 || (pss && kind == KPE_SCAN_LEAN6)) return 0;
   static thread_local int cus = 0;
   if (!cus) {
     int dev = 0;
@@ -1566,18 +1226,17 @@ extern "C" uint32_t kpe_scan_grid(int64_t n, int pss, int narrow, size_t dyn_byt
       cus = 256;
   }
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, scan_fn(pss, narrow), kBlock, dyn_bytes) != hipSuccess)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, scan_fn(pss, kind), kBlock, dyn_bytes) != hipSuccess)
     per_cu = 1;
   const int64_t tiles = (n + kBlock - 1) / kBlock;
   const int64_t g = (int64_t)cus * (per_cu > 0 ? per_cu : 1);
   return (uint32_t)(g < tiles ? g : tiles);
 }
 // `dargs` is the device copy of the arguments; `n` its row count.
-extern "C" hipError_t kpe_launch_scan(const ScanArgs* dargs, const ScanArgs* hargs, int64_t n, int pss, int narrow,
-                                      uint32_t grid, size_t dyn_bytes, hipStream_t s) {
+extern "C" hipError_t kpe_launch_scan(const ScanArgs* dargs, int64_t n, int pss, int kind, uint32_t grid,
+                                      size_t dyn_bytes, hipStream_t s) {
   if (n == 0 || grid == 0) return hipSuccess;
-  (void)hargs;
-  hipLaunchKernelGGL(scan_fn(pss, narrow), dim3(grid), dim3(kBlock), dyn_bytes, s, dargs);
+  hipLaunchKernelGGL(scan_fn(pss, kind), dim3(grid), dim3(kBlock), dyn_bytes, s, dargs);
   return hipGetLastError();
 }
 // ---- selector requirement masks (ScanArgs::selm), once per binding ----------------------------
@@ -1673,574 +1332,3 @@ extern "C" hipError_t kpe_launch_prep(const ScanArgs* dargs, int pss, int narrow
   hipLaunchKernelGGL(prep_fn(pss, narrow), dim3(1), dim3(kBlock), dyn_bytes, s, dargs);
   return hipGetLastError();
 }
-// Rows past a per-resource encoding limit (Corpus::limit_rows): every cell undecided.
-__global__ void __launch_bounds__(256) kpe_fill_rows_kernel(uint8_t* verdicts, uint32_t R, const uint32_t* rows,
-                                                            uint32_t nrows, uint8_t value) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < (uint64_t)nrows * R) verdicts[(size_t)rows[i / R] * R + i % R] = value;
-}
-extern "C" hipError_t kpe_launch_fill_rows(uint8_t* verdicts, uint32_t R, const uint32_t* rows, uint32_t nrows,
-                                           uint8_t value, hipStream_t s) {
-  const uint64_t cells = (uint64_t)nrows * R;
-  if (cells == 0) return hipSuccess;
-  hipLaunchKernelGGL(kpe_fill_rows_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, verdicts, R, rows,
-                     nrows, value);
-  return hipGetLastError();
-}
-// applyRules: One (pkg/engine/validation.go:75-77: stop after the first rule whose response is
-// pass or fail, RulesAppliedCount) over the final verdicts: cells after an applied rule of the
-// policy give no response; after an undecided cell they are undecided (unless unmatched).
-__global__ void __launch_bounds__(256) kpe_apply_one_kernel(uint8_t* verdicts, uint32_t* masks, uint32_t n, uint32_t R,
-                                                            const uint2* segs, uint32_t nsegs) {
-  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (r >= n) return;
-  uint8_t* row = verdicts + (size_t)r * R;
-#pragma unroll 1
-  for (uint32_t s = 0; s < nsegs; ++s) {
-    const uint2 sg = segs[s];
-    uint32_t state = 0;  // 0 open, 1 applied, 2 an earlier cell undecided
-#pragma unroll 1
-    for (uint32_t i = sg.x; i < sg.y; ++i) {
-      const uint32_t v = row[i];
-      if (state == 1u) {
-        if (v != KPE_NA_) {
-          row[i] = KPE_NA_;
-          if (masks) masks[(size_t)r * R + i] = 0u;
-        }
-      } else if (state == 2u) {
-        if (v != KPE_NA_) row[i] = KPE_UNDECIDED_;
-      } else if (v == KPE_PASS_ || v == KPE_FAIL_) {
-        state = 1u;
-      } else if (v == KPE_UNDECIDED_) {
-        state = 2u;
-      }
-    }
-  }
-}
-extern "C" hipError_t kpe_launch_apply_one(uint8_t* verdicts, uint32_t* masks, int64_t n, uint32_t R, const uint32_t* segs,
-                                           uint32_t nsegs, hipStream_t s) {
-  if (n <= 0 || nsegs == 0) return hipSuccess;
-  hipLaunchKernelGGL(kpe_apply_one_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, verdicts, masks,
-                     (uint32_t)n, R, reinterpret_cast<const uint2*>(segs), nsegs);
-  return hipGetLastError();
-}
-extern "C" hipError_t kpe_launch_count(const uint8_t* verdicts, int64_t n, uint32_t R, unsigned long long* out,
-                                       hipStream_t s) {
-  if (R == 0) return hipSuccess;
-  hipError_t e = hipMemsetAsync(out, 0, (size_t)R * 8 * 8, s);
-  if (e != hipSuccess || n == 0) return e;
-  const int64_t waves = (n + 63) / 64;
-  const uint32_t grid = (uint32_t)std::min<int64_t>((waves + 3) / 4, 1024);
-  for (uint32_t r0 = 0; r0 < R; r0 += 1536) {  // <= 48 KiB of LDS histogram per launch
-    const uint32_t rn = std::min<uint32_t>(1536, R - r0);
-    hipLaunchKernelGGL(kpe_count_kernel, dim3(grid), dim3(256), (size_t)rn * 8 * 4, s, verdicts, n, R, r0, rn, out);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-// ---------------------------------------------------------------------------
-// Sparse result fetch (kpe_select_cells, kpe_fetch_row_summaries): reductions of the verdict
-// matrix read as a flat array of N x R bytes, 16 cells per lane with one 16-byte load (the matrix
-// is a hipMalloc allocation, so a multiple of 16 from its base is aligned); a block tile is
-// 256 x 16 = 4096 cells. A lane's tail is bounded by count: no byte past the range is read.
-// Per-rule byte tables (the selection masks, the unscored flags) are staged in LDS up to
-// kSelLdsRules rules and read from global memory past that.
-constexpr uint32_t kSelTile = 4096;
-constexpr uint32_t kSelLdsRules = 16384;
-constexpr uint32_t kSelGrid = 2048;   // persistent blocks of the selection kernels (8 per CU: every wave slot)
-constexpr uint32_t kSumRows = 1024;   // rows a block of the summary kernel counts at a time (24 KiB of LDS)
-constexpr uint32_t kSumGrid = 1536;   // persistent blocks of the summary kernel (6 per CU: what its LDS allows)
-
-namespace {
-struct Cells16 {
-  uint32_t w[4];
-  __device__ __forceinline__ uint32_t at(uint32_t k) const {  // k: compile-time after unrolling
-    return (w[k >> 2] >> (8u * (k & 3u))) & 0xFFu;
-  }
-  __device__ __forceinline__ uint32_t at_dyn(uint32_t k) const {
-    const uint64_t lo = (uint64_t)w[0] | ((uint64_t)w[1] << 32), hi = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
-    return (uint32_t)((k < 8u ? lo >> (8u * k) : hi >> (8u * (k - 8u))) & 0xFFu);
-  }
-};
-// cells [f, f + cnt) of the matrix, cnt <= 16, f a multiple of 16
-__device__ __forceinline__ Cells16 load_cells(const uint8_t* __restrict__ v, uint64_t f, uint32_t cnt) {
-  Cells16 c;
-  if (cnt == 16u) {
-    const uint4 q = *reinterpret_cast<const uint4*>(v + f);
-    c.w[0] = q.x, c.w[1] = q.y, c.w[2] = q.z, c.w[3] = q.w;
-  } else {
-    c.w[0] = c.w[1] = c.w[2] = c.w[3] = 0u;
-#pragma unroll
-    for (uint32_t k = 0; k < 15u; ++k)
-      if (k < cnt) c.w[k >> 2] |= (uint32_t)v[f + k] << (8u * (k & 3u));
-  }
-  return c;
-}
-__device__ __forceinline__ uint32_t flat_col(uint64_t f, uint32_t R) {
-  return (f >> 32) == 0 ? (uint32_t)f % R : (uint32_t)(f % R);
-}
-// column k <= 4 cells after column col
-__device__ __forceinline__ uint32_t col_add(uint32_t col, uint32_t k, uint32_t R) {
-  col += k;
-  return col < R ? col : (R >= k ? col - R : col % R);
-}
-// bit k: cell f + k is selected (the cell's verdict v has bit v of its rule's mask set). skip_na
-// (uniform: no rule selects KPE_NA): a word of four NA cells is passed over without its table
-// reads; most cells of a wide matrix are NA. Cells past cnt are zero and never selected.
-__device__ __forceinline__ uint32_t sel_hits(const Cells16& c, uint32_t cnt, uint32_t col, uint32_t R,
-                                             const uint8_t* tbl, bool skip_na) {
-  uint32_t m = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < 4u; ++w) {
-    if (skip_na && c.w[w] == 0u) {
-      col = col_add(col, 4u, R);
-      continue;
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < 4u; ++j) {
-      const uint32_t k = 4u * w + j;
-      const uint32_t v = c.at(k);
-      const uint32_t s = tbl[col];
-      if (k < cnt && v < 8u && ((s >> v) & 1u)) m |= 1u << k;
-      col = col + 1u == R ? 0u : col + 1u;
-    }
-  }
-  return m;
-}
-// the block's per-rule byte table: staged in LDS (uniform branch), or the global one
-template <bool LDS>
-__device__ __forceinline__ const uint8_t* stage_table(const uint8_t* __restrict__ g, uint32_t R, uint8_t* lds) {
-  if (!LDS) return g;
-  for (uint32_t i = threadIdx.x; i < R; i += 256u) lds[i] = g[i];
-  __syncthreads();
-  return lds;
-}
-}  // namespace
-
-// Pass 1: selected cells per tile (popcount of each lane's 16-bit hit mask, block sum).
-template <bool LDS>
-__global__ void __launch_bounds__(256) kpe_select_count_kernel(const uint8_t* __restrict__ v, uint64_t cells, uint32_t R,
-                                                               const uint8_t* __restrict__ sel, uint32_t skip_na,
-                                                               uint32_t* __restrict__ tile_counts, uint64_t ntiles) {
-  extern __shared__ uint8_t s_sel_tbl[];
-  __shared__ uint32_t s_w[2][4];  // by tile parity: one barrier per tile
-  const uint32_t t = threadIdx.x;
-  const uint8_t* tbl = stage_table<LDS>(sel, R, s_sel_tbl);
-  uint32_t par = 0;
-  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, par ^= 1u) {
-    const uint64_t f = tile * kSelTile + t * 16u;
-    const uint32_t cnt = f >= cells ? 0u : (cells - f < 16u ? (uint32_t)(cells - f) : 16u);
-    uint32_t hits = 0;
-    if (cnt) hits = __popc(sel_hits(load_cells(v, f, cnt), cnt, flat_col(f, R), R, tbl, skip_na != 0u));
-    const uint32_t inc = wave_incl_scan(hits);
-    if ((t & 63u) == 63u) s_w[par][t >> 6] = inc;
-    __syncthreads();
-    if (t == 0) tile_counts[tile] = s_w[par][0] + s_w[par][1] + s_w[par][2] + s_w[par][3];
-  }
-}
-
-// Pass 2: exclusive 64-bit scan of the tile counts, offs[ntiles] = the total. One block, 4096
-// tiles per round (16 per thread, four 16-byte loads: tile_counts is 16-byte aligned and padded to
-// a multiple of four entries).
-__global__ void __launch_bounds__(256) kpe_select_scan_kernel(const uint32_t* __restrict__ tile_counts,
-                                                              uint64_t* __restrict__ offs, uint64_t ntiles) {
-  __shared__ uint32_t s_w[4];
-  const uint32_t t = threadIdx.x;
-  uint64_t carry = 0;
-  for (uint64_t base = 0; base < ntiles; base += 4096u) {
-    const uint64_t i0 = base + t * 16u;
-    uint32_t c[16], sum = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < 4u; ++q) {
-      uint4 x = make_uint4(0u, 0u, 0u, 0u);
-      if (i0 + 4u * q < ntiles) x = *reinterpret_cast<const uint4*>(tile_counts + i0 + 4u * q);
-      c[4u * q] = x.x, c[4u * q + 1u] = x.y, c[4u * q + 2u] = x.z, c[4u * q + 3u] = x.w;
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < 16u; ++k) {
-      if (i0 + k >= ntiles) c[k] = 0u;  // the padding
-      sum += c[k];
-    }
-    const uint32_t inc = wave_incl_scan(sum);  // <= 256 x 16 x 4096: 32 bits hold a round
-    if ((t & 63u) == 63u) s_w[t >> 6] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 4u; ++w) {
-      if (w < (t >> 6)) before += s_w[w];
-      all += s_w[w];
-    }
-    uint64_t o = carry + before + (inc - sum);
-#pragma unroll
-    for (uint32_t k = 0; k < 16u; ++k) {
-      if (i0 + k < ntiles) offs[i0 + k] = o;
-      o += c[k];
-    }
-    carry += all;
-    __syncthreads();
-  }
-  if (t == 0) offs[ntiles] = carry;
-}
-
-// Pass 3: the hit masks again; a lane's first output slot is its tile's offset + the waves before
-// it (LDS) + the lanes before it (DPP scan). Only slots below cap are written. Tiles without a
-// selected cell, and tiles that start at or past cap, are not read.
-template <bool LDS>
-__global__ void __launch_bounds__(256) kpe_select_scatter_kernel(const uint8_t* __restrict__ v, uint64_t cells, uint32_t R,
-                                                                 const uint8_t* __restrict__ sel, uint32_t skip_na,
-                                                                 const uint64_t* __restrict__ offs, uint64_t ntiles,
-                                                                 uint64_t cap, uint64_t* __restrict__ out_cells,
-                                                                 uint8_t* __restrict__ out_v) {
-  extern __shared__ uint8_t s_sel_tbl[];
-  __shared__ uint32_t s_w[4];
-  const uint32_t t = threadIdx.x;
-  const uint8_t* tbl = stage_table<LDS>(sel, R, s_sel_tbl);
-  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const uint64_t o0 = offs[tile], o1 = offs[tile + 1];  // uniform
-    if (o0 == o1 || o0 >= cap) continue;
-    const uint64_t f = tile * kSelTile + t * 16u;
-    const uint32_t cnt = f >= cells ? 0u : (cells - f < 16u ? (uint32_t)(cells - f) : 16u);
-    Cells16 c;
-    uint32_t m = 0;
-    if (cnt) {
-      c = load_cells(v, f, cnt);
-      m = sel_hits(c, cnt, flat_col(f, R), R, tbl, skip_na != 0u);
-    }
-    const uint32_t hits = __popc(m);
-    const uint32_t inc = wave_incl_scan(hits);
-    if ((t & 63u) == 63u) s_w[t >> 6] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 3u; ++w)
-      if (w < (t >> 6)) before += s_w[w];
-    uint64_t o = o0 + before + (inc - hits);
-    while (m) {
-      const uint32_t k = (uint32_t)__builtin_ctz(m);
-      m &= m - 1u;
-      if (o < cap) {
-        out_cells[o] = f + k;
-        if (out_v) out_v[o] = (uint8_t)c.at_dyn(k);
-      }
-      ++o;
-    }
-    __syncthreads();
-  }
-}
-
-// CalculateSummary per resource (pkg/utils/report/results.go:39-55 over :89-135): rows
-// [row0, row0 + nrows), 6 uint16 counters per row (pass, fail, warn, error, skip, undecided) as 3
-// words. A block takes groups of rows_per_group whole rows (<= kSumRows, about one tile of bytes),
-// reads their contiguous bytes with the aligned 16-byte loads (cells before the group's first byte
-// are skipped by index) and counts each lane's cells of one row in a register (5 bits per counter)
-// before adding them to the row's LDS counters; each row is written once. With R >= 16 a lane's 16
-// cells lie in at most two rows: two registers, no branch per cell, and words of four KPE_NA cells
-// (most of a wide matrix) are passed over. unscored[r] != 0: a FAIL of rule r counts as warn
-// (results.go:131-133).
-template <bool LDS>
-__global__ void __launch_bounds__(256) kpe_row_summary_kernel(const uint8_t* __restrict__ v, uint32_t R, uint64_t row0,
-                                                              uint64_t nrows, uint32_t rows_per_group,
-                                                              const uint8_t* __restrict__ unscored,
-                                                              uint32_t* __restrict__ out) {
-  extern __shared__ uint8_t s_sel_tbl[];
-  __shared__ uint32_t s_cnt[kSumRows * 6u];
-  const uint32_t t = threadIdx.x;
-  const uint8_t* tbl = stage_table<LDS>(unscored, R, s_sel_tbl);
-  const uint64_t ngroups = (nrows + rows_per_group - 1u) / rows_per_group;
-  // a lane's counts of one row (5 bits per counter, at most 16 cells) into the row's LDS counters
-  auto flush = [&](uint32_t acc, uint32_t lrow) {
-    while (acc) {
-      const uint32_t s = (uint32_t)__builtin_ctz(acc) / 5u;
-      atomicAdd(&s_cnt[lrow * 6u + s], (acc >> (5u * s)) & 31u);
-      acc &= ~(31u << (5u * s));
-    }
-  };
-  // the counter increment of verdict code x of rule col (0: not counted). Code -> counter + 1:
-  // PASS, FAIL (or warn), WARN, ERROR, SKIP, -, UNDECIDED
-  auto cell_inc = [&](uint32_t x, uint32_t col) -> uint32_t {
-    const uint32_t lut = 0x60543210u + (tbl[col] ? 0x100u : 0u);
-    const uint32_t slot = x < 8u ? (lut >> (4u * x)) & 15u : 0u;
-    return (1u << (5u * slot)) >> 5;
-  };
-  for (uint64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
-    const uint64_t r0 = g * rows_per_group;  // relative to row0
-    const uint32_t rn = nrows - r0 < rows_per_group ? (uint32_t)(nrows - r0) : rows_per_group;
-    for (uint32_t i = t; i < rn * 6u; i += 256u) s_cnt[i] = 0u;
-    __syncthreads();
-    const uint64_t g0 = (row0 + r0) * R, g1 = g0 + (uint64_t)rn * R;  // the group's bytes: < 2^32 of them
-    for (uint64_t c0 = (g0 & ~(uint64_t)15u) + t * 16u; c0 < g1; c0 += kSelTile) {
-      const uint32_t cnt = g1 - c0 < 16u ? (uint32_t)(g1 - c0) : 16u;
-      const uint32_t k0 = c0 < g0 ? (uint32_t)(g0 - c0) : 0u;  // c0 may start up to 15 cells before the group
-      if (k0 >= cnt) continue;
-      const Cells16 c = load_cells(v, c0, cnt);
-      const uint32_t rel = (uint32_t)(c0 + k0 - g0);
-      uint32_t lrow = rel / R, col = rel - lrow * R;
-      if (R >= 16u) {  // uniform: cell k is in row lrow, or in lrow + 1 once its column wraps
-        uint32_t acc0 = 0, acc1 = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < 4u; ++w) {
-          if (c.w[w] == 0u) continue;
-#pragma unroll
-          for (uint32_t j = 0; j < 4u; ++j) {
-            const uint32_t k = 4u * w + j;
-            const uint32_t ck = col + (k >= k0 ? k - k0 : 0u);  // < 2 R
-            const bool next = ck >= R;
-            const uint32_t inc = (k >= k0 && k < cnt) ? cell_inc(c.at(k), next ? ck - R : ck) : 0u;
-            acc0 += next ? 0u : inc;
-            acc1 += next ? inc : 0u;
-          }
-        }
-        flush(acc0, lrow);
-        flush(acc1, lrow + 1u);  // non-zero only when a counted cell lies in that row
-      } else {
-        uint32_t acc = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 16u; ++k) {
-          if (k >= k0 && k < cnt) {
-            acc += cell_inc(c.at(k), col);
-            if (++col == R) {
-              flush(acc, lrow);
-              acc = 0, col = 0, ++lrow;
-            }
-          }
-        }
-        flush(acc, lrow);
-      }
-    }
-    __syncthreads();
-    for (uint32_t i = t; i < rn * 3u; i += 256u) out[r0 * 3u + i] = s_cnt[2u * i] | (s_cnt[2u * i + 1u] << 16);
-    __syncthreads();
-  }
-}
-
-// tile_counts: ntiles words, tile_offs: ntiles + 1 offsets (the last one is the total)
-// na_selected: some rule's mask selects KPE_NA
-extern "C" hipError_t kpe_launch_select_count(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* sel,
-                                              int na_selected, uint32_t* tile_counts, uint64_t* tile_offs,
-                                              hipStream_t s) {
-  if (!cells || !R) return hipSuccess;
-  const uint64_t ntiles = (cells + kSelTile - 1u) / kSelTile;
-  const dim3 grid((unsigned)std::min<uint64_t>(ntiles, kSelGrid));
-  const uint32_t skip_na = na_selected ? 0u : 1u;
-  if (R <= kSelLdsRules)
-    hipLaunchKernelGGL(kpe_select_count_kernel<true>, grid, dim3(256), (size_t)R, s, v, cells, R, sel, skip_na,
-                       tile_counts, ntiles);
-  else
-    hipLaunchKernelGGL(kpe_select_count_kernel<false>, grid, dim3(256), 0, s, v, cells, R, sel, skip_na, tile_counts,
-                       ntiles);
-  hipLaunchKernelGGL(kpe_select_scan_kernel, dim3(1), dim3(256), 0, s, tile_counts, tile_offs, ntiles);
-  return hipGetLastError();
-}
-// out_cells / out_v (may be NULL): at least min(total, cap) entries
-extern "C" hipError_t kpe_launch_select_scatter(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* sel,
-                                                int na_selected, const uint64_t* tile_offs, uint64_t cap,
-                                                uint64_t* out_cells, uint8_t* out_v, hipStream_t s) {
-  if (!cells || !R || !cap) return hipSuccess;
-  const uint64_t ntiles = (cells + kSelTile - 1u) / kSelTile;
-  const dim3 grid((unsigned)std::min<uint64_t>(ntiles, kSelGrid));
-  const uint32_t skip_na = na_selected ? 0u : 1u;
-  if (R <= kSelLdsRules)
-    hipLaunchKernelGGL(kpe_select_scatter_kernel<true>, grid, dim3(256), (size_t)R, s, v, cells, R, sel, skip_na,
-                       tile_offs, ntiles, cap, out_cells, out_v);
-  else
-    hipLaunchKernelGGL(kpe_select_scatter_kernel<false>, grid, dim3(256), 0, s, v, cells, R, sel, skip_na, tile_offs,
-                       ntiles, cap, out_cells, out_v);
-  return hipGetLastError();
-}
-// out: 3 words per row of [row0, row0 + nrows); R <= 65535 (the counters are 16 bits wide)
-extern "C" hipError_t kpe_launch_row_summary(const uint8_t* v, uint32_t R, uint64_t row0, uint64_t nrows,
-                                             const uint8_t* unscored, uint32_t* out, hipStream_t s) {
-  if (!nrows || !R) return hipSuccess;
-  const uint32_t rpg = std::max<uint32_t>(1u, std::min<uint32_t>(kSumRows, kSelTile / R));
-  const uint64_t ngroups = (nrows + rpg - 1u) / rpg;
-  const dim3 grid((unsigned)std::min<uint64_t>(ngroups, kSumGrid));
-  if (R <= kSelLdsRules)
-    hipLaunchKernelGGL(kpe_row_summary_kernel<true>, grid, dim3(256), (size_t)R, s, v, R, row0, nrows, rpg, unscored, out);
-  else
-    hipLaunchKernelGGL(kpe_row_summary_kernel<false>, grid, dim3(256), 0, s, v, R, row0, nrows, rpg, unscored, out);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Per-namespace rule counts (kpe_fetch_namespace_counts): the verdict matrix grouped by the row's
-// namespace, 6 uint32 counters per (namespace, rule): pass, fail, warn, error, skip, undecided (raw
-// verdict codes; KPE_NA and codes outside the alphabet are not counted). The inverted-index form:
-// the host sorts the row ids by namespace once per corpus (`rows`) and cuts each namespace into
-// work items of at most kNsChunk rows (KpeNsItem). A block takes one item at a time, so every
-// contribution it sums has the same namespace, and counts in registers: a counter is a 10-bit
-// field of a 64-bit word (an item has at most 1023 rows, so no field overflows, in a lane or in a
-// sum over the block). Memory sees at most one add per (namespace, rule, counter) per item, and
-// only for non-zero counters: a plain store when the namespace is one item (the window is zeroed
-// before the launch), an integer atomic add otherwise. Integer adds only: the table is exact and
-// does not depend on the schedule.
-constexpr uint32_t kNsChunk = 512;    // rows per work item (<= 1023: the 10-bit fields)
-constexpr uint32_t kNsGrid = 2048;    // persistent blocks (8 per CU)
-constexpr uint32_t kNsNarrow = 16;    // R below this: one row per lane (kpe_ns_count_narrow_kernel)
-constexpr uint32_t kNsLdsUnits = 128; // column units a block sums in LDS (wider tiles: one lane per unit, no LDS)
-constexpr uint32_t kNsBatch = 8;      // row loads a lane keeps in flight
-static_assert(kNsChunk <= 1023u, "10-bit counters");
-
-namespace {
-// verdict code -> its 10-bit field of the packed counters (0 for codes that are not counted).
-// Code -> field: PASS 0, FAIL 1, WARN 2, ERROR 3, SKIP 4, UNDECIDED (7) 5
-__device__ __forceinline__ uint64_t ns_inc(uint32_t x) {
-  const uint32_t f = x < 8u ? (0x5F43210Fu >> (4u * x)) & 15u : 15u;
-  return f < 6u ? (uint64_t)1 << (10u * f) : (uint64_t)0;
-}
-__device__ __forceinline__ void ns_emit(uint32_t* __restrict__ o, uint32_t c, bool single) {
-  if (!c) return;
-  if (single) *o = c;
-  else atomicAdd(o, c);
-}
-}  // namespace
-
-// R >= kNsNarrow. The row is cut into units of VEC columns (VEC = 4 when R is a multiple of 4: a
-// unit is one aligned 32-bit load, and a word of four KPE_NA cells is passed over; VEC = 1
-// otherwise) and the units into tiles of W = min(units, 256). Thread t owns unit t % W of the tile
-// and the item's rows t / W, t / W + 256 / W, ...: lanes of a wave lie along the row (coalesced
-// loads, different counters). With one slice (W > 128) a lane's counters are final and go to memory
-// from registers; otherwise the slices are summed in LDS first (a lane's at most 6 * VEC non-zero
-// counters, different words for different lanes of a slice).
-template <uint32_t VEC>
-__global__ void __launch_bounds__(256) kpe_ns_count_kernel(const uint8_t* __restrict__ v, uint32_t R,
-                                                           const uint32_t* __restrict__ rows,
-                                                           const KpeNsItem* __restrict__ items, uint32_t nitems,
-                                                           uint32_t g0, uint32_t* __restrict__ out) {
-  __shared__ uint32_t s_cnt[kNsLdsUnits * 4u * 6u];
-  const uint32_t t = threadIdx.x;
-  const uint32_t units = R / VEC;  // VEC divides R
-  const uint32_t W = units < 256u ? units : 256u;
-  const uint32_t slices = 256u / W;
-  const uint32_t u = t % W, sl = t / W;
-  const bool lds = slices > 1u;  // then W <= kNsLdsUnits
-  if (lds) {
-    for (uint32_t i = t; i < W * VEC * 6u; i += 256u) s_cnt[i] = 0u;
-    __syncthreads();
-  }
-  for (uint32_t it = blockIdx.x; it < nitems; it += gridDim.x) {
-    const KpeNsItem item = items[it];
-    uint32_t* __restrict__ o = out + (size_t)(item.g - g0) * R * 6u;
-    const bool single = item.single != 0u;
-    for (uint32_t u0 = 0; u0 < units; u0 += W) {
-      const uint32_t uu = u0 + u;
-      const bool on = sl < slices && uu < units;
-      uint64_t acc[VEC];
-#pragma unroll
-      for (uint32_t j = 0; j < VEC; ++j) acc[j] = 0;
-      if (on) {
-        const uint8_t* __restrict__ base = v + (size_t)uu * VEC;
-        // the unit of one row: a 32-bit word of four cells, or one cell
-        auto load = [&](uint32_t row) -> uint32_t {
-          const uint8_t* p = base + (size_t)row * R;
-          return VEC == 4u ? *reinterpret_cast<const uint32_t*>(p) : (uint32_t)p[0];
-        };
-        auto count = [&](uint32_t w) {
-          if (w == 0u) return;  // KPE_NA cells (a word of four of them): nothing to count
-#pragma unroll
-          for (uint32_t j = 0; j < VEC; ++j) acc[j] += ns_inc((w >> (8u * j)) & 0xFFu);
-        };
-        // kNsBatch rows' loads are issued before the first is counted (the rows are a gather)
-        uint32_t i = item.begin + sl;
-        for (; i + (kNsBatch - 1u) * slices < item.end; i += kNsBatch * slices) {
-          uint32_t w[kNsBatch];
-#pragma unroll
-          for (uint32_t b = 0; b < kNsBatch; ++b) w[b] = load(rows[i + b * slices]);
-#pragma unroll
-          for (uint32_t b = 0; b < kNsBatch; ++b) count(w[b]);
-        }
-        for (; i < item.end; i += slices) count(load(rows[i]));
-      }
-      if (!lds) {
-        if (on) {
-#pragma unroll
-          for (uint32_t j = 0; j < VEC; ++j)
-#pragma unroll
-            for (uint32_t k = 0; k < 6u; ++k)
-              ns_emit(o + ((size_t)uu * VEC + j) * 6u + k, (uint32_t)(acc[j] >> (10u * k)) & 1023u, single);
-        }
-        continue;
-      }
-      if (on) {
-#pragma unroll
-        for (uint32_t j = 0; j < VEC; ++j)
-#pragma unroll
-          for (uint32_t k = 0; k < 6u; ++k) {
-            const uint32_t c = (uint32_t)(acc[j] >> (10u * k)) & 1023u;
-            if (c) atomicAdd(&s_cnt[(u * VEC + j) * 6u + k], c);
-          }
-      }
-      __syncthreads();
-      const uint32_t wn = (units - u0 < W ? units - u0 : W) * VEC * 6u;  // this tile's counters
-      for (uint32_t i = t; i < wn; i += 256u) {
-        const uint32_t c = s_cnt[i];
-        if (c) {
-          s_cnt[i] = 0u;
-          ns_emit(o + (size_t)u0 * VEC * 6u + i, c, single);
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// R < kNsNarrow (the C2 shape, R = 3): one row per lane, the row's R bytes, one packed register
-// per column. The columns' registers are summed over the wave with shuffles and over the four
-// waves through LDS (4 x R words): no atomics on a few hot LDS words.
-__global__ void __launch_bounds__(256) kpe_ns_count_narrow_kernel(const uint8_t* __restrict__ v, uint32_t R,
-                                                                  const uint32_t* __restrict__ rows,
-                                                                  const KpeNsItem* __restrict__ items, uint32_t nitems,
-                                                                  uint32_t g0, uint32_t* __restrict__ out) {
-  __shared__ uint64_t s_part[4][kNsNarrow];
-  const uint32_t t = threadIdx.x;
-  for (uint32_t it = blockIdx.x; it < nitems; it += gridDim.x) {
-    const KpeNsItem item = items[it];
-    uint64_t acc[kNsNarrow - 1u];
-#pragma unroll
-    for (uint32_t c = 0; c < kNsNarrow - 1u; ++c) acc[c] = 0;
-    for (uint32_t i = item.begin + t; i < item.end; i += 256u) {
-      const uint8_t* __restrict__ p = v + (size_t)rows[i] * R;
-#pragma unroll
-      for (uint32_t c = 0; c < kNsNarrow - 1u; ++c)
-        if (c < R) acc[c] += ns_inc(p[c]);
-    }
-#pragma unroll
-    for (uint32_t c = 0; c < kNsNarrow - 1u; ++c) {
-      if (c < R) {  // uniform
-        uint64_t a = acc[c];
-#pragma unroll
-        for (uint32_t d = 32u; d; d >>= 1) {
-          const uint32_t lo = __shfl_xor((int)(uint32_t)a, (int)d, 64), hi = __shfl_xor((int)(uint32_t)(a >> 32), (int)d, 64);
-          a += (uint64_t)lo | ((uint64_t)hi << 32);
-        }
-        if ((t & 63u) == 0u) s_part[t >> 6][c] = a;
-      }
-    }
-    __syncthreads();
-    if (t < R * 6u) {
-      const uint32_t c = t / 6u, k = t - c * 6u;
-      const uint64_t a = s_part[0][c] + s_part[1][c] + s_part[2][c] + s_part[3][c];
-      ns_emit(out + (size_t)(item.g - g0) * R * 6u + t, (uint32_t)(a >> (10u * k)) & 1023u, item.single != 0u);
-    }
-    __syncthreads();
-  }
-}
-
-// items: the work items of groups [g0, g0 + ng) (every item.g lies in it, every rows[] entry of
-// [begin, end) is a row of the matrix); out: ng x R x 6 words, zeroed by the caller on s.
-extern "C" hipError_t kpe_launch_ns_counts(const uint8_t* v, uint32_t R, const uint32_t* rows, const KpeNsItem* items,
-                                           uint64_t nitems, uint32_t g0, uint32_t* out, hipStream_t s) {
-  if (!nitems || !R) return hipSuccess;
-  if (nitems > 0xFFFFFFFFull) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)std::min<uint64_t>(nitems, kNsGrid));
-  if (R < kNsNarrow)
-    hipLaunchKernelGGL(kpe_ns_count_narrow_kernel, grid, dim3(256), 0, s, v, R, rows, items, (uint32_t)nitems, g0, out);
-  else if (R % 4u == 0u)
-    hipLaunchKernelGGL(kpe_ns_count_kernel<4u>, grid, dim3(256), 0, s, v, R, rows, items, (uint32_t)nitems, g0, out);
-  else
-    hipLaunchKernelGGL(kpe_ns_count_kernel<1u>, grid, dim3(256), 0, s, v, R, rows, items, (uint32_t)nitems, g0, out);
-  return hipGetLastError();
-}
-extern "C" uint32_t kpe_ns_chunk_rows(void) { return kNsChunk; }
-#endif  // !KPE_VM_ONLY

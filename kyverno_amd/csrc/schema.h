@@ -203,7 +203,7 @@ enum KpeDomain {
    (1u << VS_PVC) | (1u << VS_PROJECTED) | (1u << VS_SECRET))
 // Per-pod PSA summary (2 words per row, built on the device: lean.inl kpe_psum_kernel): x = OR of
 // the container state bitmaps (CX_*), y = the OR-ed list codes under the PSA library's fixed
-// sets: capability-set bits (CS_* of kernels.hip) | volume codes << 3 (bit 0 hostPath, bit 1 a
+// sets: capability-set bits (CS_* of scan.hip) | volume codes << 3 (bit 0 hostPath, bit 1 a
 // source outside PSS_ALLOWED_VOLUMES) | sysctl codes << 5 (bit v: a sysctl outside version v's
 // set) | annotation codes << 8 (bit 0 AppArmor, bit 1 pod seccomp annotation not allowed) | bit
 // 10: a container's seccomp annotation (c_sann) outside the allowed profiles (check_seccompProfile

@@ -1,5 +1,5 @@
 // go-wildcard v1.0.3 glob and k8s validation predicates over byte strings. Device code
-// (included by kernels.hip inside its anonymous namespace); also compiled for the host by
+// (included by kernels_common.h inside its anonymous namespace); also compiled for the host by
 // scripts/patvm_check.cpp so the pattern VM can be exercised under sanitizers.
 
 // ---------------------------------------------------------------------------

@@ -34,7 +34,7 @@ import kyverno_amd as K  # noqa: E402
 from kyverno_amd._lib import check, load  # noqa: E402
 
 HBM_PEAK = 8.0e12
-CHUNK = 512  # rows per work item (kernels.hip kNsChunk)
+CHUNK = 512  # rows per work item (results.hip kNsChunk)
 SHAPES = {"c2": 1_000_000, "c3": 1_250_000}
 
 

@@ -35,7 +35,7 @@ static std::vector<uint32_t> summary(const Corpus& C) {
     if (pssfix::fixed_match(pssfix::kCapNbs, c)) nbs |= 1ull << i;
     if (pssfix::fixed_match(pssfix::kCapAll, c)) all |= 1ull << i;
   }
-  // kernels.hip CS_BASE / CS_DROP / CS_ADD per capability set
+  // scan.hip CS_BASE / CS_DROP / CS_ADD per capability set
   std::vector<uint8_t> csb(C.capset_add.size());
   for (size_t j = 0; j < csb.size(); ++j) {
     const uint64_t ad = C.capset_add[j], dr = C.capset_drop[j];
