@@ -286,15 +286,69 @@ struct LeanBatchArgs {
   uint32_t nshards, nrules, ncls, cv_union, pss_rules, err_rules, pat_rules, need;
   uint32_t kt_words, code_words, wave_words, tpw;  // LDS: kind table, codes (LC), per-wave stage
   const uint32_t* narrow_cls;  // (cv classes, rule mask) pairs of the program
+  // the first KPE_L6_CLS version classes as evidence masks (below; zero past ncls): a pod fails
+  // class c when its evidence word meets ev[c], or ev_nw[c] on a pod that is not a Windows pod
+  uint32_t cls_ev[4], cls_ev_nw[4], cls_rm[4];
   uint32_t blk0[KPE_LEAN_BATCH + 1];  // a block covers 4 * tpw tiles of 64 pods
   LeanShard sh[KPE_LEAN_BATCH];
 };
-// Per-wave LDS stage of kpe_lean6_kernel: a tile's staged list items (container codes as uint2,
+// Per-wave LDS stage of kpe_lean6_kernel: a tile's staged list items (one word per container,
 // volume / sysctl / annotation codes as bytes); items past these counts are loaded again.
 #define KPE_L6_CTR 128u
 #define KPE_L6_VOL 128u
 #define KPE_L6_SMALL 64u
-#define KPE_L6_STAGE_BYTES (KPE_L6_CTR * 8u + KPE_L6_VOL + 2u * KPE_L6_SMALL)
+#define KPE_L6_STAGE_BYTES (KPE_L6_CTR * 4u + KPE_L6_VOL + 2u * KPE_L6_SMALL)
+// A staged container: the state bits the PSA checks read (CX_*, in place) with the container's
+// codes in bits those leave free: its capability-set code (CS_* of scan.hip) and whether its
+// seccomp annotation is outside the allowed profiles. The word of an empty slot is 0.
+#define KPE_L6_CX_USED                                                                                          \
+  (CX_PRIV_T | CX_APE_T | CX_APE_U | CX_RNR_F | CX_RNR_U | CX_RAU_Z | CX_SEC_NONE | CX_SEC_UNC | CX_SEC_OTHER | \
+   CX_PM_OTHER | CX_SEL_OTHER | CX_SEL_USER | CX_SEL_ROLE | CX_WHP_T | CX_HOSTPORT)
+#define KPE_L6_CAP_SH 26   // 3 bits (CX_WHP_NT, CX_CAPS, CX_NOCAPS are not read)
+#define KPE_L6_SANN_SH 30  // 1 bit (CX_NOHOSTPORT)
+// The evidence word of a pod (verdict-only evaluations): the OR of its staged containers, with the
+// pod-level fields folded into the container bits they are alternatives of (a pod-level
+// runAsUser: 0 sets CX_RAU_Z, a valid pod seccomp type clears CX_SEC_NONE, ...), and the pod's
+// list codes and host namespaces in further free bits. Every versioned check is then "some bit
+// of kpe_l6_evidence(cv) is set", so a version class fails when the word meets the OR of its
+// checks' masks.
+#define KPE_L6_CLS 4u
+#define KPE_L6_EV_SYS0 (1u << 1)   // sysctl outside the 1.0 / 1.27 / 1.29 sets: bits 1, 2, 4
+#define KPE_L6_EV_SYS1 (1u << 2)
+#define KPE_L6_EV_SYS2 (1u << 4)
+#define KPE_L6_EV_HOSTNS (1u << 6)
+#define KPE_L6_VOL_SH 13           // volume code: bit 0 hostPath, bit 1 outside the restricted set
+#define KPE_L6_ANN_SH 17           // annotation code: bit 0 AppArmor, bit 1 pod seccomp annotation
+// Evidence bits of versioned check cv; *nw: the check does not apply to Windows pods.
+static inline uint32_t kpe_l6_evidence(uint32_t cv, bool* nw) {
+  *nw = cv == CV_APE_1_25 || cv == CV_CAPS_RESTRICTED_1_25 || cv == CV_SECCOMP_RESTRICTED_1_25;
+  switch (cv) {
+    case CV_APE_1_8:
+    case CV_APE_1_25: return CX_APE_T | CX_APE_U;
+    case CV_APPARMOR_1_0: return 1u << KPE_L6_ANN_SH;
+    case CV_CAPS_BASELINE_1_0: return 1u << KPE_L6_CAP_SH;
+    case CV_CAPS_RESTRICTED_1_22:
+    case CV_CAPS_RESTRICTED_1_25: return 6u << KPE_L6_CAP_SH;
+    case CV_HOST_NS_1_0: return KPE_L6_EV_HOSTNS;
+    case CV_HOST_PATH_1_0: return 1u << KPE_L6_VOL_SH;
+    case CV_HOST_PORTS_1_0: return CX_HOSTPORT;
+    case CV_PRIVILEGED_1_0: return CX_PRIV_T;
+    case CV_PROC_MOUNT_1_0: return CX_PM_OTHER;
+    case CV_RESTRICTED_VOLUMES_1_0: return 2u << KPE_L6_VOL_SH;
+    case CV_RUN_AS_NON_ROOT_1_0: return CX_RNR_F | CX_RNR_U;
+    case CV_RUN_AS_USER_1_23: return CX_RAU_Z;
+    case CV_SELINUX_1_0: return CX_SEL_OTHER | CX_SEL_USER | CX_SEL_ROLE;
+    case CV_SECCOMP_BASELINE_1_0: return (2u << KPE_L6_ANN_SH) | (1u << KPE_L6_SANN_SH);
+    case CV_SECCOMP_BASELINE_1_19: return CX_SEC_UNC | CX_SEC_OTHER;
+    case CV_SECCOMP_RESTRICTED_1_19:
+    case CV_SECCOMP_RESTRICTED_1_25: return CX_SEC_UNC | CX_SEC_OTHER | CX_SEC_NONE;
+    case CV_SYSCTLS_1_0: return KPE_L6_EV_SYS0;
+    case CV_SYSCTLS_1_27: return KPE_L6_EV_SYS1;
+    case CV_SYSCTLS_1_29: return KPE_L6_EV_SYS2;
+    case CV_WIN_HOST_PROCESS_1_0: return CX_WHP_T;
+    default: return 0u;
+  }
+}
 
 // kpe_pattern_kernel arguments (device-resident, one copy per binding)
 struct PatArgs {

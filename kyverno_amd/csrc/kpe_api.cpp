@@ -124,7 +124,9 @@ struct kpe_device {
   int last_kind = 0;
   // knobs, read once at kpe_device_open: KPE_NO_BIND_CACHE (recompute per-binding products every
   // evaluation), KPE_PATVM_ERR (report a KPE_PATVM_CHECK build's bounds flags), KPE_LEAN6_MINW /
-  // KPE_LEAN6_TPW (waves a LEAN6 launch keeps / tiles per wave, for A/B runs)
+  // KPE_LEAN6_TPW (waves a LEAN6 launch keeps / tiles per wave, for A/B runs), KPE_LEAN6_SHAPE
+  // (A/B runs: bit 0 the instantiation that reads the seccomp annotations, bit 1 the one that
+  // decides every versioned check, for programs that need neither)
   bool no_cache = false, patvm_err = false;
   // the general scan of a podSecurity program walks each pod's lists itself; KPE_PSUM=1: it reads
   // per-pod records kpe_psum_kernel builds right before it on the second stream (round 6: C4 step
@@ -132,7 +134,7 @@ struct kpe_device {
   // records for their 0.92x traffic against 1.98x: profiles/r05_psA, r05_psB, r05_final5)
   bool no_psum = true;
   uint64_t lean_min_waves = 16384;  // 256 CUs x 4 SIMDs x 16 waves
-  uint32_t lean_tpw = 0;
+  uint32_t lean_tpw = 0, lean_shape = 0;
   // pinned staging for corpus uploads (two halves, double-buffered; allocated on first use): a
   // pageable hipMemcpyAsync is staged by the runtime chunk by chunk, a pinned one is one DMA
   static constexpr size_t kStageHalf = 16u << 20;
@@ -165,6 +167,7 @@ struct DeviceProgram {
   bool narrow = false;  // per-lane rule loop (kernels_abi.h NR_*)
   bool tt = false;      // + truth-table fast path
   uint32_t ncls = 0, pss_rules = 0, err_rules = 0, pat_rules = 0;
+  std::vector<uint32_t> cls_h;  // host copy of narrow_cls: (cv_mask, rule mask) per version class
   // pattern rules: compiled trees + operand records (program.hpp PatProgram)
   DevBuf pnodes, plists, pleaves, pconds, ppats, pbytes, proots, prules;
   DevBuf plslot, pslot_leaf;  // leaf-table slot per leaf, leaf per slot (PatArgs::lslot)
@@ -308,6 +311,7 @@ kpe_status kpe_device_open(int ordinal, kpe_device** out) {
     const int t = atoi(ev);
     d->lean_tpw = t == 1 || t == 2 || t == 4 ? (uint32_t)t : 0u;
   }
+  if (const char* ev = getenv("KPE_LEAN6_SHAPE")) d->lean_shape = (uint32_t)atoi(ev) & 3u;
   for (int k = 0; k < d->nlanes; ++k) {
     e = hipStreamCreateWithFlags(&d->lanes[k], hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -676,6 +680,7 @@ kpe_status ensure_program(kpe_device* dev, const kpe_program* pp) {
   D.narrow = narrow;
   D.tt = tt;
   D.ncls = (uint32_t)cls.size() / 2;
+  D.cls_h = cls;
   D.pss_rules = pss_rules;
   D.err_rules = err_rules;
   D.pat_rules = pat_rules;
@@ -1861,9 +1866,22 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
   a.blk0[m] = acc;
   a.kt_words = (kt_max + 3u) & ~3u;
   a.code_words = lc ? ((code_max + 15u) / 16u) * 4u : 0u;
-  a.wave_words = ((KPE_L6_STAGE_BYTES + 64u * R + 15u) / 16u) * 4u;
+  a.wave_words = ((KPE_L6_STAGE_BYTES + std::max(64u * R, 256u) + 15u) / 16u) * 4u;  // rows: a word per pod at least
+  // the kernel's shape: check masks, or more version classes than the evidence masks hold, take
+  // the instantiation that decides every versioned check; the others decide classes
+  const bool cv = masks || PD.ncls > KPE_L6_CLS || (dev->lean_shape & 2u);
+  if (!cv)
+    for (uint32_t c = 0; c < PD.ncls; ++c) {
+      const uint32_t checks = PD.cls_h[2 * c] & P.cv_union;
+      for (uint32_t v = 0; v < KPE_NUM_CV; ++v) {
+        bool nw;
+        const uint32_t ev = kpe_l6_evidence(v, &nw);
+        if ((checks >> v) & 1u) (nw ? a.cls_ev_nw : a.cls_ev)[c] |= ev;
+      }
+      a.cls_rm[c] = PD.cls_h[2 * c + 1];
+    }
   const size_t dyn = 4 * ((size_t)a.kt_words + a.code_words + 4 * (size_t)a.wave_words);
-  HIPCHK(kpe_launch_lean6(&a, dyn, lc ? 1 : 0, s));
+  HIPCHK(kpe_launch_lean6(&a, dyn, lc ? 1 : 0, (a.need & NEED_SANN) || (dev->lean_shape & 1u) ? 1 : 0, cv ? 1 : 0, s));
   return KPE_OK;
 }
 

@@ -211,26 +211,51 @@ __global__ void __launch_bounds__(256) kpe_psum_kernel(PsumArgs a) {
 // scalar binary search over LeanBatchArgs::blk0). Two dependent memory steps per wave:
 //   1. the T + 1 tile headers (one dword per lane) and the T tiles' pod records (16 B per lane);
 //   2. every tile's list items, cooperatively and coalesced: lane i loads container i and 64 + i
-//      of the tile (crec, and c_sann when a v1.0 seccomp check runs), volumes i and 64 + i,
-//      sysctl i and annotation i, from the tile's first item (header) on.
+//      of the tile (crec, and c_sann in the SANN instantiations: programs with a v1.0 seccomp
+//      check), volumes i and 64 + i, sysctl i and annotation i, from the tile's first item on.
 // Then per tile: lane i codes its staged items (capability-set / sysctl / annotation codes from
-// the corpus's code bytes, LDS-staged per block when they fit: LC) into the wave's LDS stage, each
-// pod ORs its own items from there (its offsets: one wave scan of the packed list counts), pods
-// with more items than the clamped reads cover (or items past the stage) loop over the rest, the
-// PSA checks are decided (cv_fails), masked by the program's version classes and the kind table,
-// and the tile's rows are stored as dwords through LDS (with the failing versioned checks per
-// cell in the masks mode).
+// the corpus's code bytes, LDS-staged per block when they fit: LC) into the wave's LDS stage (a
+// container as one word: kernels_abi.h KPE_L6_*), each pod ORs its own items from there (its
+// offsets: one wave scan of the packed list counts), pods with more items than the clamped reads
+// cover (or items past the stage) loop over the rest, the program's version classes are decided
+// and the tile's rows are stored as dwords through LDS.
+// How a class is decided is the CV parameter. CV: every versioned check (cv_fails), masked by the
+// class's checks; needed for the check masks per cell (LeanShard::masks) and taken by programs of
+// more than KPE_L6_CLS classes. Otherwise (verdicts only): one AND of the pod's evidence word
+// with the class's evidence mask (LeanBatchArgs::cls_ev). Both give the same verdicts.
 typedef const __attribute__((address_space(4))) LeanBatchArgs CBArgs;
 typedef const __attribute__((address_space(4))) LeanShard CShard;
-struct L6Items {
+template <bool SANN>
+struct L6Items;
+template <>
+struct L6Items<false> {
   uint2 c0, c1, q0;
-  uint32_t v0, v1, s0, a0, a1;
+  uint32_t v0, v1, s0;
 };
-template <int T, bool LC>
+template <>
+struct L6Items<true> : L6Items<false> {
+  uint32_t a0, a1;
+};
+// The pod word's part of the evidence word: bits to set and container bits to clear.
+__device__ __forceinline__ void l6_pod_evidence(uint32_t pw, uint32_t& set, uint32_t& clr) {
+  const uint32_t prnr = FIELD(pw, P_RNR_SH, 2), psel = FIELD(pw, P_SEL_SH, 3), psec = FIELD(pw, P_SECCOMP_SH, 3);
+  constexpr uint32_t kSecValid = (1u << SECCOMP_RUNTIMEDEFAULT) | (1u << SECCOMP_LOCALHOST);
+  constexpr uint32_t kSecBad = 0xFFu & ~kSecValid & ~(1u << SECCOMP_NONE);
+  const bool sel_bad = psel != SEL_NONE && (psel == SEL_OTHER || (pw & (P_SEL_USER | P_SEL_ROLE)));
+  set = ((pw & (P_HOSTNET | P_HOSTPID | P_HOSTIPC)) ? KPE_L6_EV_HOSTNS : 0u) | (prnr == TRI_FALSE ? CX_RNR_F : 0u) |
+        (FIELD(pw, P_RAU_SH, 2) == RAU_ZERO ? CX_RAU_Z : 0u) | (sel_bad ? CX_SEL_OTHER : 0u) |
+        (((kSecBad >> psec) & 1u) ? CX_SEC_UNC : 0u) | (FIELD(pw, P_WHP_SH, 2) == TRI_TRUE ? CX_WHP_T : 0u);
+  clr = (prnr == TRI_TRUE ? CX_RNR_U : 0u) | (((kSecValid >> psec) & 1u) ? CX_SEC_NONE : 0u);
+}
+// sysctl code (bit v: outside version v's set) at its evidence bits
+__device__ __forceinline__ uint32_t l6_sys_evidence(uint32_t c) { return ((c & 3u) << 1) | ((c & 4u) << 2); }
+
+template <int T, bool LC, bool SANN, bool CV>
 __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBatchArgs) {
   extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
   CBArgs& a = *(CBArgs*)kargs();
-  const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+  const uint32_t t = threadIdx.x, lane = t & 63u;
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(t >> 6);  // in a scalar: so are the wave's tile numbers
   const uint32_t gb = xcd_block(blockIdx.x, gridDim.x);
   uint32_t lo = 0, hi = a.nshards;  // blk0[lo] <= gb < blk0[hi]
   while (hi - lo > 1u) {
@@ -246,7 +271,7 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
   // no data (so do loads past a column's end)
   const Rsrc REC = make_rsrc(S.rec, n * 16u), HDR = make_rsrc(S.hdr, (ntiles + 1u) * 16u);
   const Rsrc CREC = make_rsrc(S.crec, S.nctr * 8u);
-  const Rsrc SAN = make_rsrc(S.sann, (need & NEED_SANN) ? S.nctr * 4u : 0u);
+  const Rsrc SAN = make_rsrc(S.sann, SANN && (need & NEED_SANN) ? S.nctr * 4u : 0u);
   const Rsrc VOL = make_rsrc(S.vol, (need & NEED_VOL) ? S.nvol * 4u : 0u);
   const Rsrc SYS = make_rsrc(S.sys, (need & NEED_SYS) ? S.nsys * 4u : 0u);
   const Rsrc ANN = make_rsrc(S.pann, (need & NEED_PANN) ? S.npann * 8u : 0u);
@@ -262,7 +287,7 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
   const uint32_t* gcw = reinterpret_cast<const uint32_t*>(S.codes);
   const uint32_t cw0 = LC && t < ncw ? gcw[t] : 0u;
   // ---- step 2: the list items of every tile
-  L6Items it[T];
+  L6Items<SANN> it[T];
 #pragma unroll
   for (int j = 0; j < T; ++j) {
     if (tile0 + j >= ntiles) break;
@@ -270,8 +295,10 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
                    A0 = hw(hall, 4u * j + 3u);
     it[j].c0 = bload2(CREC, (C0 + lane) * 8u);
     it[j].c1 = bload2(CREC, (C0 + 64u + lane) * 8u);
-    it[j].a0 = bload1(SAN, (C0 + lane) * 4u);
-    it[j].a1 = bload1(SAN, (C0 + 64u + lane) * 4u);
+    if constexpr (SANN) {
+      it[j].a0 = bload1(SAN, (C0 + lane) * 4u);
+      it[j].a1 = bload1(SAN, (C0 + 64u + lane) * 4u);
+    }
     it[j].v0 = bload1(VOL, (V0 + lane) * 4u);
     it[j].v1 = bload1(VOL, (V0 + 64u + lane) * 4u);
     it[j].s0 = bload1(SYS, (S0 + lane) * 4u);
@@ -288,7 +315,7 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
   }
   uint32_t cls_cv = 0, cls_rm = 0;
   const uint32_t ncls = a.ncls;
-  if (lane < ncls) {
+  if (CV && lane < ncls) {
     const uint2 c = reinterpret_cast<const uint2*>(a.narrow_cls)[lane];
     cls_cv = c.x, cls_rm = c.y;
   }
@@ -300,24 +327,49 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
   L.ncapsets = S.L.ncapsets, L.nsysd = S.L.nsysd, L.nannk = S.L.nannk, L.nannv = S.L.nannv;
   L.o_sys = S.L.o_sys, L.o_annk = S.L.o_annk, L.o_annv = S.L.o_annv, L.bytes = S.L.bytes;
   const PsaCoder K{L};
-  const bool nsann = need & NEED_SANN, nvol = need & NEED_VOL, nsys = need & NEED_SYS, npann = need & NEED_PANN;
-  auto ctr_code = [&](uint2 e, uint32_t cs) -> uint2 {  // a real container record always has state bits
-    const uint32_t sa = nsann ? K.sann(cb, cs) << 3 : 0u;
-    return make_uint2(e.x, K.cap(cb, e) | (e.x ? sa : 0u));
+  const bool nvol = need & NEED_VOL, nsys = need & NEED_SYS, npann = need & NEED_PANN;
+  // a container's stage word (a real record always has state bits, tested before they are masked)
+  auto ctr_word = [&](uint2 e, uint32_t cs) -> uint32_t {
+    uint32_t w = (e.x & KPE_L6_CX_USED) | ((cb(CY_CAPSET(e.y)) & 7u) << KPE_L6_CAP_SH);
+    if constexpr (SANN) w |= K.sann(cb, cs) << KPE_L6_SANN_SH;
+    return e.x ? w : 0u;
   };
+  // sysctl codes are staged where the pod's word wants them: cv_fails's argument, or evidence bits
+  auto sys_code = [&](uint32_t id) -> uint32_t { return CV ? K.sys(cb, id) : l6_sys_evidence(K.sys(cb, id)); };
+  // the version classes' evidence masks, in scalars for every tile
+  uint32_t cev[KPE_L6_CLS], cev_nw[KPE_L6_CLS], crm[KPE_L6_CLS];
+#pragma unroll
+  for (uint32_t c = 0; c < KPE_L6_CLS; ++c) {
+    cev[c] = CV ? 0u : a.cls_ev[c], cev_nw[c] = CV ? 0u : a.cls_ev_nw[c], crm[c] = CV ? 0u : a.cls_rm[c];
+    asm volatile("" : "+s"(cev[c]), "+s"(cev_nw[c]), "+s"(crm[c]));
+  }
   const uint32_t R = a.nrules, cv_union = a.cv_union, pss_rules = a.pss_rules;
   const uint32_t ep_rules = a.err_rules | a.pat_rules, pat_rules = a.pat_rules;
   uint8_t* const stg = reinterpret_cast<uint8_t*>(cl + a.code_words + wv * a.wave_words);
-  uint2* const sc = reinterpret_cast<uint2*>(stg);
-  uint8_t* const sbv = stg + 8u * KPE_L6_CTR;
+  uint32_t* const sc = reinterpret_cast<uint32_t*>(stg);
+  uint8_t* const sbv = stg + 4u * KPE_L6_CTR;
   uint8_t* const sbs = sbv + KPE_L6_VOL;
   uint8_t* const sba = sbs + KPE_L6_SMALL;
-  uint8_t* const sv = sba + KPE_L6_SMALL;  // the tile's verdict rows (64 x R bytes)
+  uint8_t* const sv = sba + KPE_L6_SMALL;  // the tile's verdict rows (64 x R bytes; 256 at least)
+  // Rows of 2 to 4 bytes: a full tile's rows leave as one dword store per lane. Lane i's dword is
+  // bytes 4 i .. 4 i + 3 of the tile's rows: they lie in the rows of pod rp_cell and the next one,
+  // picked out of those two pods' cell words by the byte selector rp_sel.
+  const bool rpack = R - 2u <= 2u;
+  uint32_t rp_cell = 0, rp_sel = 0;
+  if (rpack) {
+    const uint32_t b = 4u * lane, p0 = R == 3u ? (b * 171u) >> 9 : b >> (R >> 1), r0 = b - p0 * R;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+      const uint32_t g = r0 + k;
+      rp_sel |= (g >= R ? 4u + g - R : g) << (8u * k);
+    }
+    rp_cell = min(p0, 63u);
+  }
 #pragma unroll
   for (int j = 0; j < T; ++j) {
     const uint32_t tile = tile0 + j;
     if (tile >= ntiles) break;
-    const L6Items& d = it[j];
+    const L6Items<SANN>& d = it[j];
     const uint32_t C0 = hw(hall, 4u * j), V0 = hw(hall, 4u * j + 1u), S0 = hw(hall, 4u * j + 2u),
                    A0 = hw(hall, 4u * j + 3u);
     const uint32_t nct = hw(hall, 4u * j + 4u) - C0, nvt = hw(hall, 4u * j + 5u) - V0,
@@ -339,21 +391,21 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
     // stage the codes of the loaded slots (slots past the tile's items hold codes of the next
     // tile's items, or of zeros past a column's end, that no pod reads)
     __builtin_amdgcn_wave_barrier();  // the previous tile's stage reads are done
-    sc[lane] = ctr_code(d.c0, d.a0);
-    sc[lane + 64u] = ctr_code(d.c1, d.a1);
+    if constexpr (SANN) {
+      sc[lane] = ctr_word(d.c0, d.a0), sc[lane + 64u] = ctr_word(d.c1, d.a1);
+    } else {
+      sc[lane] = ctr_word(d.c0, 0u), sc[lane + 64u] = ctr_word(d.c1, 0u);
+    }
     if (nvol) sbv[lane] = (uint8_t)vol_code(d.v0), sbv[lane + 64u] = (uint8_t)vol_code(d.v1);
-    if (nsys && nst) sbs[lane] = (uint8_t)K.sys(cb, d.s0);
+    if (nsys && nst) sbs[lane] = (uint8_t)sys_code(d.s0);
     if (npann && nat) sba[lane] = (uint8_t)K.ann(cb, d.q0);
     __builtin_amdgcn_wave_barrier();
     // each pod ORs its first items with clamped reads (a repeated item does not change an OR)
-    uint32_t xo, co, vcode = 0, scode = 0, acode = 0;
+    uint32_t cw, vcode = 0, scode = 0, acode = 0;
     {
       const uint32_t last = min(oc + (nc ? nc - 1u : 0u), KPE_L6_CTR - 1u);
-      const uint2 e0 = sc[min(oc, last)], e1 = sc[min(oc + 1u, last)], e2 = sc[min(oc + 2u, last)],
-                  e3 = sc[min(oc + 3u, last)];
-      const uint32_t m = nc ? ~0u : 0u;
-      xo = (e0.x | e1.x | e2.x | e3.x) & m;
-      co = (e0.y | e1.y | e2.y | e3.y) & m;
+      const uint32_t x = sc[min(oc, last)] | sc[min(oc + 1u, last)] | sc[min(oc + 2u, last)] | sc[min(oc + 3u, last)];
+      cw = nc ? x : 0u;
     }
     if (nvol) {
       const uint32_t last = min(ov + (nv ? nv - 1u : 0u), KPE_L6_VOL - 1u);
@@ -378,12 +430,10 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
     const bool more_c = nc > 4u, more_v = nvol && nv > 4u, more_s = nsys && ns > 2u, more_a = npann && na > 2u;
     if (tile_over || __builtin_amdgcn_ballot_w64(more_c || more_v || more_s || more_a)) {
       if (more_c || oc + nc > KPE_L6_CTR) {
-        xo = co = 0;
-        for (uint32_t k = oc; k < oc + nc; ++k) {
-          const uint2 e = k < KPE_L6_CTR ? sc[k]
-                                         : ctr_code(bload2(CREC, (C0 + k) * 8u), nsann ? bload1(SAN, (C0 + k) * 4u) : 0u);
-          xo |= e.x, co |= e.y;
-        }
+        cw = 0;
+        for (uint32_t k = oc; k < oc + nc; ++k)
+          cw |= k < KPE_L6_CTR ? sc[k]
+                               : ctr_word(bload2(CREC, (C0 + k) * 8u), SANN ? bload1(SAN, (C0 + k) * 4u) : 0u);
       }
       if (nvol && (more_v || ov + nv > KPE_L6_VOL)) {
         vcode = 0;
@@ -393,7 +443,7 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
       if (nsys && (more_s || os + ns > KPE_L6_SMALL)) {
         scode = 0;
         for (uint32_t k = os; k < os + ns; ++k)
-          scode |= k < KPE_L6_SMALL ? (uint32_t)sbs[k] : K.sys(cb, bload1(SYS, (S0 + k) * 4u));
+          scode |= k < KPE_L6_SMALL ? (uint32_t)sbs[k] : sys_code(bload1(SYS, (S0 + k) * 4u));
       }
       if (npann && (more_a || oa + na > KPE_L6_SMALL)) {
         acode = 0;
@@ -403,45 +453,75 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
     }
     // ---- the PSA checks, the rule match (kind table) and the verdict bytes ----
     const uint32_t pw = rec[j].x;
-    const uint32_t fails =
-        cv_fails(pw, xo, co & 7u, (co >> 3) & 1u, vcode & 1u, vcode & 2u, scode, acode & 1u, acode & 2u) & cv_union;
+    uint32_t fails = 0, failr = 0;
+    if constexpr (CV) {
+      fails = cv_fails(pw, cw & KPE_L6_CX_USED, (cw >> KPE_L6_CAP_SH) & 7u, (cw >> KPE_L6_SANN_SH) & 1u, vcode & 1u,
+                       vcode & 2u, scode, acode & 1u, acode & 2u) &
+              cv_union;
+      if (ncls <= 4u) {  // the usual few version classes: no loop
+#pragma unroll
+        for (uint32_t c = 0; c < 4u; ++c)
+          failr |= (c < ncls && (fails & hw(cls_cv, c))) ? hw(cls_rm, c) : 0u;
+      } else {
+#pragma unroll 1
+        for (uint32_t c = 0; c < ncls; ++c) failr |= (fails & hw(cls_cv, c)) ? hw(cls_rm, c) : 0u;
+      }
+    } else {
+      uint32_t set, clr;
+      l6_pod_evidence(pw, set, clr);
+      const uint32_t ev = (cw & ~clr) | set | (vcode << KPE_L6_VOL_SH) | scode | (acode << KPE_L6_ANN_SH);
+      const uint32_t nwin = FIELD(pw, P_OS_SH, 2) == OS_WINDOWS ? 0u : ~0u;
+#pragma unroll
+      for (uint32_t c = 0; c < KPE_L6_CLS; ++c) {
+        if (c >= ncls) break;
+        failr |= (ev & (cev[c] | (cev_nw[c] & nwin))) ? crm[c] : 0u;
+      }
+    }
     const uint32_t cls = (pw >> PR_CLASS_SH) & R_CLASS_MASK;
     const bool err = cls == R_CLASS_OTHER || (pw & PR_DECODE_ERR);
     const uint32_t kind = GVK_KIND(rec[j].y);
     const uint32_t matched = live && kind < nk ? dyn[kind] : 0u;
-    uint32_t failr = 0;
-    if (ncls <= 4u) {  // the usual few version classes: no loop
-#pragma unroll
-      for (uint32_t c = 0; c < 4u; ++c)
-        failr |= (c < ncls && (fails & hw(cls_cv, c))) ? hw(cls_rm, c) : 0u;
-    } else {
-#pragma unroll 1
-      for (uint32_t c = 0; c < ncls; ++c) failr |= (fails & hw(cls_cv, c)) ? hw(cls_rm, c) : 0u;
-    }
     const uint32_t E = matched & ((err ? pss_rules : 0u) | ep_rules);
     const uint32_t F = (matched & pss_rules & failr & ~E) | (matched & pat_rules);  // F|E = PENDING
     const uint32_t P = matched & pss_rules & ~failr & ~E;
-    if (R <= 4u) {  // (C2: R = 3) the row's bytes without a loop
+    const uint32_t nrows = min(64u, n - tile * 64u);
+    bool stored = false;
+    if (R <= 4u) {  // (C2: R = 3) the row as one word, byte ri = rule ri's cell: each 4-bit mask spread
+      // over the bytes by a 24-bit multiply (bit i to bit 7 i + i) at its cell bit
+      constexpr uint32_t kSpread = 0x204081u, kOnes = 0x01010101u;
+      const uint32_t cellw = (__umul24(P, kSpread) & kOnes) | (__umul24(F, kSpread << 1) & (kOnes << 1)) |
+                             (__umul24(E, kSpread << 2) & (kOnes << 2));
+      if (rpack && nrows == 64u) {
+        uint32_t* const sw = reinterpret_cast<uint32_t*>(sv);
+        sw[lane] = cellw;
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t w0 = sw[rp_cell], w1 = sw[min(rp_cell + 1u, 63u)];
+        if (lane < 16u * R)
+          reinterpret_cast<uint32_t*>(S.verdicts + (size_t)tile * (64u * R))[lane] = __builtin_amdgcn_perm(w1, w0, rp_sel);
+        stored = true;
+      } else {
 #pragma unroll
-      for (uint32_t ri = 0; ri < 4u; ++ri)
-        if (ri < R)
-          sv[lane * R + ri] = (uint8_t)(((P >> ri) & 1u) | (((F >> ri) & 1u) << 1) | (((E >> ri) & 1u) << 2));
+        for (uint32_t ri = 0; ri < 4u; ++ri)
+          if (ri < R) sv[lane * R + ri] = (uint8_t)(cellw >> (8u * ri));
+      }
     } else {
 #pragma unroll 1
       for (uint32_t ri = 0; ri < R; ++ri)
         sv[lane * R + ri] = (uint8_t)(((P >> ri) & 1u) | (((F >> ri) & 1u) << 1) | (((E >> ri) & 1u) << 2));
     }
-    if (S.masks && live) {
-      uint32_t* mrow = S.masks + (size_t)r * R;
-      const uint32_t fm = F & pss_rules;
+    if constexpr (CV) {
+      if (S.masks && live) {
+        uint32_t* mrow = S.masks + (size_t)r * R;
+        const uint32_t fm = F & pss_rules;
 #pragma unroll 1
-      for (uint32_t ri = 0; ri < R; ++ri) {
-        uint32_t cv = 0;
-        for (uint32_t c = 0; c < ncls; ++c) cv = ((hw(cls_rm, c) >> ri) & 1u) ? hw(cls_cv, c) : cv;
-        mrow[ri] = ((fm >> ri) & 1u) ? (fails & cv) : 0u;
+        for (uint32_t ri = 0; ri < R; ++ri) {
+          uint32_t cv = 0;
+          for (uint32_t c = 0; c < ncls; ++c) cv = ((hw(cls_rm, c) >> ri) & 1u) ? hw(cls_cv, c) : cv;
+          mrow[ri] = ((fm >> ri) & 1u) ? (fails & cv) : 0u;
+        }
       }
     }
     __builtin_amdgcn_wave_barrier();
-    store_rows(S.verdicts, sv, tile, R, 0, R, min(64u, n - tile * 64u), lane);
+    if (!stored) store_rows(S.verdicts, sv, tile, R, 0, R, nrows, lane);
   }
 }

@@ -1300,16 +1300,32 @@ extern "C" hipError_t kpe_launch_selmask(const SelMaskArgs* a, hipStream_t s) {
   return hipGetLastError();
 }
 // The LEAN evaluation of one or more bound shards of one program in one grid (lean.inl).
-// tpw: tiles per wave (1, 2 or 4; 4 only with the code bytes in LDS, lc).
-extern "C" hipError_t kpe_launch_lean6(const LeanBatchArgs* a, size_t dyn_bytes, int lc, hipStream_t s) {
+// tpw: tiles per wave (1, 2 or 4; 4 only with the code bytes in LDS, lc). sann: the program has a
+// v1.0 seccomp check (reads c_sann); cv: every versioned check is decided (check masks, or more
+// than KPE_L6_CLS version classes). Without the code bytes in LDS (rare: > 8 KiB of codes) the
+// one instantiation that covers every program runs.
+template <int T, bool LC>
+static void lean6_go(int sann, int cv, dim3 g, dim3 b, size_t dyn_bytes, hipStream_t s, const LeanBatchArgs& a) {
+  if constexpr (!LC) {
+    hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, true>), g, b, dyn_bytes, s, a);
+  } else {
+    if (sann && cv) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, true>), g, b, dyn_bytes, s, a);
+    else if (sann) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, false>), g, b, dyn_bytes, s, a);
+    else if (cv) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, false, true>), g, b, dyn_bytes, s, a);
+    else hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, false, false>), g, b, dyn_bytes, s, a);
+  }
+}
+extern "C" hipError_t kpe_launch_lean6(const LeanBatchArgs* a, size_t dyn_bytes, int lc, int sann, int cv,
+                                       hipStream_t s) {
   const uint32_t grid = a->blk0[a->nshards];
   if (a->nshards == 0 || grid == 0) return hipSuccess;
+  if (!cv && a->ncls > KPE_L6_CLS) return hipErrorInvalidValue;
   const dim3 g(grid), b(kLB);
-  if (a->tpw == 4 && lc) hipLaunchKernelGGL((kpe_lean6_kernel<4, true>), g, b, dyn_bytes, s, *a);
-  else if (a->tpw == 2 && lc) hipLaunchKernelGGL((kpe_lean6_kernel<2, true>), g, b, dyn_bytes, s, *a);
-  else if (a->tpw == 1 && lc) hipLaunchKernelGGL((kpe_lean6_kernel<1, true>), g, b, dyn_bytes, s, *a);
-  else if (a->tpw == 2) hipLaunchKernelGGL((kpe_lean6_kernel<2, false>), g, b, dyn_bytes, s, *a);
-  else if (a->tpw == 1) hipLaunchKernelGGL((kpe_lean6_kernel<1, false>), g, b, dyn_bytes, s, *a);
+  if (a->tpw == 4 && lc) lean6_go<4, true>(sann, cv, g, b, dyn_bytes, s, *a);
+  else if (a->tpw == 2 && lc) lean6_go<2, true>(sann, cv, g, b, dyn_bytes, s, *a);
+  else if (a->tpw == 1 && lc) lean6_go<1, true>(sann, cv, g, b, dyn_bytes, s, *a);
+  else if (a->tpw == 2) lean6_go<2, false>(sann, cv, g, b, dyn_bytes, s, *a);
+  else if (a->tpw == 1) lean6_go<1, false>(sann, cv, g, b, dyn_bytes, s, *a);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }

@@ -3,9 +3,9 @@
 
     pmc_waves.py <rocprofv3 -d dir> <kernel name prefix>
 
-Sums each counter over a dispatch's rows, takes the median dispatch of the kernels whose name
-starts with the prefix, and prints the totals and the per-wave figures (SQ_WAVE_CYCLES counts
-quad-cycles on gfx950, MI355X_MICROARCH.md)."""
+Sums each counter over a dispatch's rows, takes the median dispatch of each kernel (template
+instantiations apart) whose name starts with the prefix, and prints the totals and the per-wave
+figures (SQ_WAVE_CYCLES counts quad-cycles on gfx950, MI355X_MICROARCH.md)."""
 import collections
 import csv
 import glob
@@ -25,11 +25,13 @@ def main():
     if not per:
         sys.exit(f"no dispatch of {prefix} under {d}")
     counters = sorted({c for v in per.values() for c in v})
-    med = {c: statistics.median(v.get(c, 0.0) for v in per.values()) for c in counters}
-    waves = med.get("SQ_WAVES", 0.0) or 1.0
-    print(f"{prefix}: {len(per)} dispatches (median)")
-    for c in counters:
-        print(f"  {c:20s} {med[c]:16.0f}  per wave {med[c] / waves:10.1f}")
+    for name in sorted({k for k, _ in per}):
+        rows = [v for (k, _), v in per.items() if k == name]
+        med = {c: statistics.median(v.get(c, 0.0) for v in rows) for c in counters}
+        waves = med.get("SQ_WAVES", 0.0) or 1.0
+        print(f"{name}: {len(rows)} dispatches (median)")
+        for c in counters:
+            print(f"  {c:20s} {med[c]:16.0f}  per wave {med[c] / waves:10.1f}")
 
 
 if __name__ == "__main__":
