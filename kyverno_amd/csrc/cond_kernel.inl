@@ -15,8 +15,11 @@ namespace {
 // anyPattern entries (the VM's frame stack and code stay out of the plain instance)
 // Programs with partial-string variables (VT_TMPL) get 2 x KPE_TXT_CAP bytes of dynamic LDS per
 // lane for the substituted key / value strings; the others launch without it.
+// Two waves per SIMD (four 128-lane blocks per CU, what the LDS of a program with partial-string
+// variables allows): the register allocator keeps each instance within 256 VGPRs.
 template <bool FEPAT>
-__global__ void __launch_bounds__(128) kpe_cond_kernel(const CondArgs* __restrict__ ap) {
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2)))
+kpe_cond_kernel(const CondArgs* __restrict__ ap) {
   __shared__ char nb[128][2][16];
   extern __shared__ __attribute__((aligned(16))) uint8_t ctx[];
   const int64_t i = (int64_t)blockIdx.x * 128 + threadIdx.x;

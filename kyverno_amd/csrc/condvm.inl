@@ -8,7 +8,8 @@
 //   anyin.go, allin.go, anynotin.go, allnotin.go, in.go, notin.go
 //   engine.go:278-285 (preconditions), validate_resource.go:186-279 (foreach, deny),
 //   utils/foreach.go:12-63 (EvaluateList, AddElementToContext)
-//   go-jmespath (go.mod:33) field / index / flatten / projection / multi-select / keys / `||`
+//   go-jmespath (go.mod:33) field / index / flatten / projection / multi-select / keys / `||`,
+//   functions.go length / keys / values / contains / starts_with / ends_with / not_null
 // Every function is forced inline and each heavy one has a single call site (cond_eval_row is a
 // state machine around one block() call): a call would receive the lane's private list buffers
 // through a generic `this` pointer (the same constraint as patvm.inl). Nothing recurses.
@@ -302,8 +303,10 @@ struct CondVM {
             keys_pending = true;  // fused with the `[]` that follows (compile-time check)
           }
           break;
-        case QO_VALS:  // (compile time: never inside a projection)
+        case QO_VALS:   // (compile time: never inside a projection)
+        case QO_FVALS:  // values(<chain>): a list with its nulls, an error on anything but an object
           if (type(cur) != JT_OBJ) {
+            if (op == QO_FVALS) return CS_ERROR;  // values: invalid type
             mode = 2;
             break;
           } else {
@@ -312,7 +315,8 @@ struct CondVM {
             const uint32_t b = doc[cur.p].y, c0 = b + 1u, end = c0 + doc[b].x;
             for (uint32_t c = c0; c < end; ++c)
               if (push(fb, node(c))) return CS_UNDEC;
-            lb = fb, mode = 1;
+            if (op == QO_VALS) lb = fb, mode = 1;
+            else cur = cv(VK_LIST, fb);
           }
           break;
         case QO_FLAT:
@@ -411,18 +415,76 @@ struct CondVM {
     return CS_OK;
   }
   // A query with its `||` operands: the first truthy one, else the last one's value.
+  // An operand that is a call (CE_CALL: contains / starts_with / ends_with / not_null, go-jmespath
+  // functions.go) has its arguments evaluated one after another through the same run_ops() site,
+  // each with its own `||` operands and all of them before any type check (as the interpreter
+  // does); `held` keeps argument 0 (not_null: the first non-null one so far). A held list lives
+  // in b0 / b1, so a later argument that would write those buffers makes the cell undecided, as
+  // does a contains() needle that is a list or an object against an array (a deep comparison).
   __device__ __forceinline__ int query(uint32_t ei, uint32_t b0, uint32_t b1, CV* out) {
+    uint32_t ci = CE_NONE;  // the open call's expression | its current argument << 24 (program.cpp
+                            // keeps both in range); little state stays live across run_ops()
+    CV held = cv(VK_NULL, 0);
     for (;;) {
       const KpeCExpr e = a.exprs[ei];
+      if (e.flags & CE_CALL) {
+        ci = ei, held = cv(VK_NULL, 0);
+        ei = a.ops[e.op0].y;
+        continue;
+      }
+      if (held.k == VK_LIST && (e.flags & CE_BUFS)) return CS_UNDEC;
       CV r;
       const int st = run_ops(e, b0, b1, &r);
       if (st == CS_NOTFOUND) return CS_ERROR;  // NotFoundError => "Unknown key" => RuleError
       if (st != CS_OK) return st;
-      if (e.alt == CE_NONE || !is_false(r)) {
-        *out = r;
-        return CS_OK;
+      if (e.alt != CE_NONE && is_false(r)) {
+        ei = e.alt;
+        continue;
       }
-      ei = e.alt;
+      if (ci != CE_NONE) {  // r is argument argi of the open call
+        const KpeCExpr call = a.exprs[ci & 0xFFFFFFu];
+        const uint32_t fn = CE_FN(call.flags), argi = ci >> 24;
+        if (argi == 0u || (fn == CF_NOT_NULL && type(held) == JT_NULL)) held = r;
+        if (argi + 1u < call.nops) {
+          ci += 1u << 24;
+          ei = a.ops[call.op0 + argi + 1u].y;
+          continue;
+        }
+        if (fn == CF_NOT_NULL) {
+          r = held;
+        } else {  // held = the subject, r = the needle / prefix / suffix
+          const uint32_t ts = type(held), tn = type(r);
+          bool h = false;
+          if (fn == CF_CONTAINS && ts == JT_ARR) {  // some element deep-equals the needle (type-strict)
+            if (tn == JT_ARR || tn == JT_OBJ) return CS_UNDEC;
+            const uint32_t n = alen(held);
+            for (uint32_t k = 0; k < n && !h; ++k) {
+              const CV x = aget(held, k);
+              if (type(x) != tn) continue;
+              h = tn == JT_NULL || (tn == JT_BOOL && btrue(x) == btrue(r)) || (tn == JT_NUM && num(x) == num(r)) ||
+                  (tn == JT_STR && seq(str(x), str(r)));
+            }
+          } else if (ts != JT_STR || tn != JT_STR) {
+            return CS_ERROR;  // invalid type
+          } else {  // bytes of p at some offset (contains), at 0 (starts_with), at the end (ends_with)
+            const SView s = str(held), p = str(r);
+            if (p.n <= s.n) {
+              int o = fn == CF_ENDS_WITH ? s.n - p.n : 0;
+              const int oe = fn == CF_CONTAINS ? s.n - p.n : o;
+              for (; o <= oe && !h; ++o) h = bytes_eq(s.s + o, p.s, p.n);
+            }
+          }
+          const uint32_t ct = a.ops[call.op0 + call.nops].y;  // the constants `true`, `false`
+          r = cv(VK_CONST, h ? ct : ct + 1u);
+        }
+        ci = CE_NONE, held = cv(VK_NULL, 0);
+        if (call.alt != CE_NONE && is_false(r)) {  // the call as a `||` operand
+          ei = call.alt;
+          continue;
+        }
+      }
+      *out = r;
+      return CS_OK;
     }
   }
   // substituteVariablesIfAny (variables/vars.go:311-389) of a string with variables inside it:

@@ -1201,8 +1201,11 @@ CondMsgs cond_msgs(const JV* j) {
 //     `[*]`, `.[a, b]` multi-select of relative field chains, keys(@), `||` with a literal or
 //     another chain, raw-string and JSON literals, length(<chain>) and `<chain> | length(@)`
 //     (functions.go jpfLength: runes of a string, items of an array, members of an object, else
-//     an invalid-type error). Parse errors of an empty expression are run-time errors; anything
-//     outside the subset is refused;
+//     an invalid-type error), keys(<chain>) / values(<chain>) in function form, and the calls
+//     contains / starts_with / ends_with / not_null as the whole query or an operand of its
+//     top-level `||` (arguments: `||` chains of the chains above, no other call; arity checked
+//     here). Parse errors of an empty expression are run-time errors; anything outside the subset
+//     is refused;
 //   * operators Equals / NotEquals / AnyIn / AllIn / AnyNotIn / AllNotIn / In / NotIn
 //     (variables/operator/*.go); InRange values of set operators are refused (as the oracle).
 namespace cq {
@@ -1453,6 +1456,7 @@ class QueryParser {
     }
     t_ = lex(q);
     i_ = 0;
+    in_call_ = false;
     if (std::any_of(t_.begin(), t_.end(), [](const Token& t) { return t.t == T_PIPE; })) {
       // `<chain> | length(@)`, the one pipe on the device: the pipe binds loosest (a `||` would
       // sit inside one of its sides), so no `||` is accepted with it
@@ -1469,30 +1473,9 @@ class QueryParser {
       CP.exprs.push_back(e);
       return (uint32_t)CP.exprs.size() - 1;
     }
-    std::vector<std::vector<uint32_t>> chains;
-    std::vector<bool> plain;
-    for (;;) {
-      bool pl = true;
-      chains.push_back(chain(&pl));
-      plain.push_back(pl);
-      if (cur().t == T_OR) {
-        ++i_;
-        continue;
-      }
-      break;
-    }
+    const uint32_t head = or_chain(true);
     if (cur().t != T_EOF) throw CompileError("JMESPath expression outside the device subset: " + q);
-    // `a || b || c`: left-associative N_OR nodes; the first truthy operand wins, else the last
-    uint32_t next = CE_NONE;
-    for (size_t k = chains.size(); k-- > 0;) {
-      KpeCExpr e{(uint32_t)CP.ops.size() / 2, (uint32_t)chains[k].size() / 2, 0, next};
-      // strict (NotFoundError on a missing member) only for a query that is one plain chain
-      if (chains.size() == 1 && plain[k]) e.flags |= CE_STRICT;
-      CP.ops.insert(CP.ops.end(), chains[k].begin(), chains[k].end());
-      CP.exprs.push_back(e);
-      next = (uint32_t)CP.exprs.size() - 1;
-    }
-    return next;
+    return head;
   }
 
  private:
@@ -1500,6 +1483,91 @@ class QueryParser {
   Consts& K;
   std::vector<Token> t_;
   size_t i_ = 0;
+  bool in_call_ = false;     // inside a call's argument list
+  bool last_proj_ = false;   // the chain just parsed ended inside a projection
+  uint32_t ctrue_ = CE_NONE;  // the interned JSON `true` (the next constant is `false`)
+  struct Operand {
+    std::vector<uint32_t> ops;
+    uint32_t flags;
+    bool plain;
+  };
+  // `a || b || c`: left-associative N_OR nodes; the first truthy operand wins, else the last.
+  // An operand is a chain or (top: the whole query's operands only) a call. Returns the first
+  // operand's expression.
+  uint32_t or_chain(bool top) {
+    std::vector<Operand> v;
+    for (;;) {
+      Operand x{{}, 0u, true};
+      if (top && cur().t == T_ID && peek().t == T_LPAREN && call_fn(cur().s) >= 0) {
+        x.flags = CE_CALL | (uint32_t)call_fn(cur().s) << 8;
+        x.ops = call();
+        x.plain = false;
+      } else {
+        x.ops = chain(&x.plain);
+        for (size_t k = 0; k < x.ops.size(); k += 2) {
+          const uint32_t o = QO_OP(x.ops[k]);
+          if (o == QO_FLAT || o == QO_STAR || o == QO_KEYS || o == QO_VALS || o == QO_FVALS || o == QO_MSL)
+            x.flags |= CE_BUFS;
+        }
+      }
+      v.push_back(std::move(x));
+      if (cur().t == T_OR) {
+        ++i_;
+        continue;
+      }
+      break;
+    }
+    uint32_t next = CE_NONE;
+    for (size_t k = v.size(); k-- > 0;) {
+      const bool is_call = v[k].flags & CE_CALL;
+      // a call's ops end with the record of its boolean constants, which is not an argument
+      KpeCExpr e{(uint32_t)CP.ops.size() / 2, (uint32_t)v[k].ops.size() / 2 - (is_call ? 1u : 0u), v[k].flags, next};
+      // strict (NotFoundError on a missing member) only for a query that is one plain chain
+      if (top && v.size() == 1 && v[k].plain) e.flags |= CE_STRICT;
+      CP.ops.insert(CP.ops.end(), v[k].ops.begin(), v[k].ops.end());
+      CP.exprs.push_back(e);
+      next = (uint32_t)CP.exprs.size() - 1;
+    }
+    return next;
+  }
+  // go-jmespath functions.go: the builtins the condition VM evaluates as calls (CF_*)
+  static int call_fn(const std::string& s) {
+    if (s == "contains") return (int)CF_CONTAINS;
+    if (s == "starts_with") return (int)CF_STARTS_WITH;
+    if (s == "ends_with") return (int)CF_ENDS_WITH;
+    if (s == "not_null") return (int)CF_NOT_NULL;
+    return -1;
+  }
+  // <fn>(<arg>, ...): every argument a `||` chain of device chains (keys(<chain>) / values(<chain>)
+  // included, no other call); the arity go-jmespath checks at run time is checked here
+  std::vector<uint32_t> call() {
+    const std::string fn = cur().s;
+    i_ += 2;
+    std::vector<uint32_t> o;
+    in_call_ = true;
+    for (;;) {
+      op(o, QO_CARG, or_chain(false));
+      if (cur().t == T_RPAREN) break;
+      if (cur().t != T_COMMA) throw CompileError("JMESPath call argument outside the device subset: " + fn + "()");
+      ++i_;
+    }
+    ++i_;
+    in_call_ = false;
+    const size_t n = o.size() / 2;
+    if (fn == "not_null" ? n < 1 : n != 2) throw CompileError("JMESPath: invalid arity for " + fn + "()");
+    // condvm.inl query() keeps the call's expression and argument number in one word
+    if (n > 16 || CP.exprs.size() >= (1u << 24))
+      throw CompileError("JMESPath: call too large for the device: " + fn + "()");
+    if (ctrue_ == CE_NONE) {
+      JV b;
+      b.t = JV::Bool, b.b = true;
+      ctrue_ = K.scalar(b);
+      b.b = false;
+      K.scalar(b);
+    }
+    op(o, QO_CONST, ctrue_);
+    return o;
+  }
   const Token& cur() const { return t_[i_]; }
   const Token& peek(size_t k = 1) const { return t_[std::min(i_ + k, t_.size() - 1)]; }
   static void op(std::vector<uint32_t>& o, uint32_t x, uint32_t y = 0) { o.push_back(x), o.push_back(y); }
@@ -1530,18 +1598,32 @@ class QueryParser {
   }
   std::vector<uint32_t> chain(bool* plain) {
     std::vector<uint32_t> o;
+    last_proj_ = false;
     // ---- root ----
     if (cur().t == T_RAW || cur().t == T_LIT) {
       op(o, QO_CONST, K.value(cur().lit));
       ++i_;
       *plain = false;
-      if (cur().t != T_OR && cur().t != T_EOF) throw CompileError("JMESPath: steps after a literal are not supported");
+      if (cur().t != T_OR && cur().t != T_EOF && !(in_call_ && (cur().t == T_COMMA || cur().t == T_RPAREN)))
+        throw CompileError("JMESPath: steps after a literal are not supported");
       return o;
     }
     if (cur().t != T_ID) throw CompileError("JMESPath root outside the device subset");
     const std::string r = cur().s;
     ++i_;
+    if ((r == "keys" || r == "values") && cur().t == T_LPAREN) {  // function form: a list, no further steps
+      ++i_;
+      bool pl = true;
+      o = chain(&pl);
+      // (a projection's list is never an object: every evaluation would be an invalid-type error)
+      if (cur().t != T_RPAREN || last_proj_) throw CompileError(r + "() argument outside the device subset");
+      ++i_;
+      op(o, r == "keys" ? QO_KEYS : QO_FVALS);
+      *plain = false;
+      return o;
+    }
     if (r == "length" && cur().t == T_LPAREN) {  // length(<chain>): a number, no further steps
+      if (in_call_) throw CompileError("length() inside a call's argument is not supported on the device");
       ++i_;
       bool pl = true;
       o = chain(&pl);
@@ -1628,6 +1710,7 @@ class QueryParser {
       }
     }
     if (keys_open) throw CompileError("keys(@) inside a projection must be flattened");
+    last_proj_ = proj;
     return o;
   }
 };

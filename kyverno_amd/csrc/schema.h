@@ -718,6 +718,9 @@ typedef struct KpePatRule {
                       // types an invalid-type error
 #define QO_IMG 12u    // images: the resource's images context map (context.go:306-348), absent
                       // when the resource has no images
+#define QO_FVALS 15u  // values(<chain>) in function form: the member values of an object as a list
+                      // (nulls kept); any other type, null included, an invalid-type error
+#define QO_CARG 16u   // an argument of a call expression (CE_CALL): y = the argument's expression
 #define QO_OP(x) ((x) & 0xFFu)
 #define QO_ARG(x) ((x) >> 8)
 typedef struct KpeCExpr {
@@ -726,6 +729,17 @@ typedef struct KpeCExpr {
   uint32_t alt;        // `||` right operand (an expression index) or 0xFFFFFFFF
 } KpeCExpr;
 #define CE_STRICT 1u
+// A function call (go-jmespath functions.go jpfContains / jpfStartsWith / jpfEndsWith /
+// jpfNotNull): ops [op0, op0 + nops) are its QO_CARG arguments, each an expression of its own
+// (with its `||` operands, never strict); ops[op0 + nops] is a QO_CONST record whose constant is
+// the JSON `true` of a boolean result, and the constant after it `false`.
+#define CE_CALL 2u
+#define CE_BUFS 4u  // the expression's ops may write the lane's list buffers
+#define CE_FN(flags) (((flags) >> 8) & 0xFFu)
+#define CF_CONTAINS 0u
+#define CF_STARTS_WITH 1u
+#define CF_ENDS_WITH 2u
+#define CF_NOT_NULL 3u
 #define CE_NONE 0xFFFFFFFFu
 // Value template: a condition key / value after variable substitution
 #define VT_CONST 0u  // a = constant
