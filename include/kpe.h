@@ -272,6 +272,68 @@ kpe_status kpe_fetch_row_summaries(kpe_device* dev, const kpe_program* prog, con
 kpe_status kpe_row_summaries_host(const kpe_program* prog, const uint8_t* verdicts, uint64_t nrows,
                                   kpe_row_summary* out);
 
+/* ---- result deltas ---------------------------------------------------------- */
+/* Which reports change after a policy or PolicyException change. The background controller
+ * re-evaluates every resource, keeps the results of unchanged policies (pkg/controllers/report/
+ * background/controller.go:379-389,392-419) and writes a report only when it differs from the stored
+ * one (storeReport returns on ReportsAreIdentical, controller.go:463, pkg/controllers/report/utils/
+ * utils.go:66-88). For a resident corpus: keep the verdict matrix of one evaluation on the device,
+ * evaluate the new program, and fetch only the rows that differ.
+ *
+ * kpe_results_keep: after kpe_evaluate / kpe_evaluate_async of prog on the corpus (KPE_E_STATE
+ * without one, like kpe_select_cells), copy the corpus's N x R verdict matrix device to device into a
+ * buffer the corpus owns, with R and the rules' "<policy>/<rule>" names (prog may be freed
+ * afterwards). The copy is enqueued behind the evaluation and ahead of the corpus's next one, which
+ * overwrites the matrix; the call does not wait for it. A kept result replaces the previous one and
+ * lives until kpe_results_drop, kpe_corpus_upload or kpe_corpus_free. It costs N x R bytes of device
+ * memory (HBM) per kept corpus. */
+kpe_status kpe_results_keep(kpe_device* dev, const kpe_program* prog, kpe_corpus* c);
+kpe_status kpe_results_drop(kpe_device* dev, kpe_corpus* c);
+/* The kept R, or -1 when nothing is kept; the name of kept rule r (owned by the corpus, NULL when
+ * r is out of range or nothing is kept). */
+int kpe_results_kept_rules(const kpe_corpus* c);
+const char* kpe_results_kept_rule_name(const kpe_corpus* c, int r);
+/* old_of[r], for every rule r of prog: the kept column whose rule name equals
+ * kpe_program_rule_name(prog, r), or -1. KPE_E_STATE when nothing is kept; KPE_E_INVALID for a name
+ * that occurs twice among the kept rules or among prog's (the map would be ambiguous: pass one of
+ * your own). Host only. */
+kpe_status kpe_delta_column_map(const kpe_corpus* c, const kpe_program* prog, int32_t* old_of);
+/* The rows of the last evaluation of prog on the corpus (the new matrix, Rn rules) that differ from
+ * the kept one (Ro rules). With old(i, r) = kept[i][old_of[r]], or KPE_NA when old_of[r] is -1, row
+ * i is changed iff
+ *   - new[i][r] != old(i, r) for some new column r, or
+ *   - (always[r] >> new[i][r]) & 1 for some new column r (the `sel` convention of kpe_select_cells:
+ *     KPE_SEL(KPE_FAIL) | KPE_SEL(KPE_ERROR) | KPE_SEL(KPE_SKIP) on the columns of an edited policy
+ *     counts the cells whose message may differ under an equal verdict; PASS and NA cells, whose
+ *     report entry is constant, are still compared), or
+ *   - a kept column that no old_of[r] names holds a code other than KPE_NA in row i (a rule that
+ *     disappeared).
+ * old_of: Rn entries, NULL = kpe_delta_column_map; always: Rn bytes, NULL = all zero. Writes the first
+ * min(total, cap) changed row indices, ascending, into rows[] and, when verdict_rows is not NULL,
+ * those rows of the new matrix (Rn bytes each) into verdict_rows[]; memory past that is not written.
+ * rows == NULL with cap == 0 counts only. Returns the total number of changed rows, or -kpe_status:
+ * KPE_E_INVALID for a null argument, cap > 0 without rows, an old_of entry below -1 or not below the
+ * kept R, or a kept column named twice; KPE_E_LIMIT when either side has more than KPE_DELTA_MAX_RULES
+ * rules (the kernel stages the kept rows of a row group and the per-rule tables in LDS); all checked
+ * before any device call. KPE_E_STATE when nothing is kept, the corpus has no evaluation of prog, or
+ * it is uploaded to another device. */
+#define KPE_DELTA_MAX_RULES 4096
+int64_t kpe_changed_rows(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const int32_t* old_of,
+                         const uint8_t* always, uint64_t* rows, uint8_t* verdict_rows, uint64_t cap);
+/* What a policy edit does to the cluster: per new column r the table out[r * 64 + old * 8 + new] of
+ * rows by kept and new verdict code (old = KPE_NA for an unmapped column); a column's table sums to
+ * N. out: Rn x 64 counters. Arguments, map and errors as kpe_changed_rows. */
+kpe_status kpe_delta_transitions(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const int32_t* old_of,
+                                 uint64_t* out);
+/* The same over two matrices the caller holds (old_v: n x Ro, new_v: n x Rn; old_of: Rn entries,
+ * required): the specification of the device calls, and what a caller without a resident corpus
+ * uses. No rule limit. Host only; no device call. */
+int64_t kpe_changed_rows_host(const uint8_t* old_v, const uint8_t* new_v, uint64_t n, uint32_t Ro, uint32_t Rn,
+                              const int32_t* old_of, const uint8_t* always, uint64_t* rows, uint8_t* verdict_rows,
+                              uint64_t cap);
+kpe_status kpe_delta_transitions_host(const uint8_t* old_v, const uint8_t* new_v, uint64_t n, uint32_t Ro, uint32_t Rn,
+                                      const int32_t* old_of, uint64_t* out);
+
 /* ---- per-namespace rule counts ---------------------------------------------- */
 /* The verdict matrix reduced by namespace group on the device: per (group, rule) the cells of each
  * raw verdict code. `fail` counts KPE_FAIL cells whether or not the policy is scored, `warn`

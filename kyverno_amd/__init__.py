@@ -22,6 +22,9 @@ from .engine import (  # noqa: F401
     Device,
     Engine,
     EngineResponse,
+    changed_rows,
+    column_map,
+    delta_transitions,
     evaluate_sharded,
     packed_words,
     unpack_verdicts,
@@ -37,10 +40,11 @@ from .engine import (  # noqa: F401
     synth_ns_labels,
     synth_resources,
 )
-from .scan import BackgroundScanner, resource_hash, resource_hashes  # noqa: F401
+from .scan import BackgroundScanner, ResidentScanner, resource_hash, resource_hashes  # noqa: F401
 
 __all__ = [
     "BackgroundScanner",
+    "ResidentScanner",
     "Corpus",
     "Device",
     "Engine",
@@ -55,6 +59,9 @@ __all__ = [
     "cli_summary_ns",
     "namespace_counts",
     "row_summaries",
+    "changed_rows",
+    "column_map",
+    "delta_transitions",
     "synth_ns_labels",
     "synth_resources",
     "load",

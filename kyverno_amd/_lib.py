@@ -89,6 +89,25 @@ def load():
     L.kpe_fetch_row_summaries.restype = ctypes.c_int
     L.kpe_row_summaries_host.argtypes = [vp, vp, ctypes.c_uint64, vp]
     L.kpe_row_summaries_host.restype = ctypes.c_int
+    u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+    L.kpe_results_keep.argtypes = [vp, vp, vp]
+    L.kpe_results_keep.restype = ctypes.c_int
+    L.kpe_results_drop.argtypes = [vp, vp]
+    L.kpe_results_drop.restype = ctypes.c_int
+    L.kpe_results_kept_rules.argtypes = [vp]
+    L.kpe_results_kept_rules.restype = ctypes.c_int
+    L.kpe_results_kept_rule_name.argtypes = [vp, i32]
+    L.kpe_results_kept_rule_name.restype = cp
+    L.kpe_delta_column_map.argtypes = [vp, vp, vp]
+    L.kpe_delta_column_map.restype = ctypes.c_int
+    L.kpe_changed_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64]
+    L.kpe_changed_rows.restype = i64
+    L.kpe_delta_transitions.argtypes = [vp, vp, vp, vp, vp]
+    L.kpe_delta_transitions.restype = ctypes.c_int
+    L.kpe_changed_rows_host.argtypes = [vp, vp, u64, u32, u32, vp, vp, vp, vp, u64]
+    L.kpe_changed_rows_host.restype = i64
+    L.kpe_delta_transitions_host.argtypes = [vp, vp, u64, u32, u32, vp, vp]
+    L.kpe_delta_transitions_host.restype = ctypes.c_int
     L.kpe_corpus_num_namespaces.argtypes = [vp]
     L.kpe_corpus_num_namespaces.restype = i64
     L.kpe_corpus_namespace.argtypes = [vp, i64]

@@ -60,4 +60,17 @@ hipError_t kpe_launch_row_summary(const uint8_t* v, uint32_t R, uint64_t row0, u
 hipError_t kpe_launch_ns_counts(const uint8_t* v, uint32_t R, const uint32_t* rows, const KpeNsItem* items,
                                 uint64_t nitems, uint32_t g0, uint32_t* out, hipStream_t s);
 uint32_t kpe_ns_chunk_rows(void);
+// result deltas (kpe_changed_rows, kpe_delta_transitions). tab: Rn words, the kept column of new
+// column r in bits 0-15 (0xFFFF: none) and its `always` mask in bits 16-23; unmapped: Ro bytes,
+// non-zero for a kept column no new column names (NULL: there is none); flags: n bytes, one per
+// row, each written once. Rn, Ro <= kpe_delta_max_rules().
+hipError_t kpe_launch_delta_flags(const uint8_t* vnew, const uint8_t* vold, uint64_t n, uint32_t Rn, uint32_t Ro,
+                                  const uint32_t* tab, const uint8_t* unmapped, uint8_t* flags, hipStream_t s);
+// out: nrows x R bytes, row i = row rows[i] of v
+hipError_t kpe_launch_gather_rows(const uint8_t* v, uint32_t R, const uint64_t* rows, uint64_t nrows, uint8_t* out,
+                                  hipStream_t s);
+// out: Rn x 64 counters (old code x 8 + new code), zeroed here
+hipError_t kpe_launch_delta_transitions(const uint8_t* vnew, const uint8_t* vold, uint64_t n, uint32_t Rn, uint32_t Ro,
+                                        const uint32_t* tab, unsigned long long* out, hipStream_t s);
+uint32_t kpe_delta_max_rules(void);
 }

@@ -265,6 +265,11 @@ struct DeviceCorpus {
   DevBuf ns_out;  // the counters of a small window (kpe_fetch_namespace_counts keeps up to 4 MiB)
   std::vector<uint64_t> ns_item_off;
   bool ns_ready = false;
+  // the kept result (kpe_results_keep): a copy of one evaluation's N x kept_rules verdict matrix and
+  // its rules' names. It belongs to the corpus, not to the binding: the next program's bind leaves it.
+  DevBuf kept;
+  int64_t kept_rules = -1;  // -1: nothing kept
+  std::vector<std::string> kept_names;
 };
 }  // namespace kpe
 
@@ -2242,6 +2247,266 @@ kpe_status kpe_fetch_row_summaries(kpe_device* dev, const kpe_program* prog, con
   uint8_t* d_uns = scratch.as<uint8_t>() + out_bytes;
   HIPCHK(hipMemcpyAsync(d_uns, unscored.data(), R, hipMemcpyHostToDevice, s));
   HIPCHK(kpe_launch_row_summary(B.verdicts.as<uint8_t>(), (uint32_t)R, row0, nrows, d_uns, scratch.as<uint32_t>(), s));
+  HIPCHK(hipMemcpyAsync(out, scratch.p, out_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return KPE_OK;
+}
+
+// ---- result deltas: a kept matrix per corpus, changed rows, transition tables ------------------
+kpe_status kpe_results_keep(kpe_device* dev, const kpe_program* prog, kpe_corpus* c) {
+  if (!dev || !prog || !c) return fail(KPE_E_INVALID, "null argument");
+  if (!c->d) return fail(KPE_E_STATE, "corpus not uploaded");
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  kpe::DeviceCorpus& D = *c->d;
+  auto& B = D.bind;
+  if (B.prog != prog->p.get()) return fail(KPE_E_STATE, "no evaluation of this program on this corpus");
+  if (D.ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  const kpe::Program& P = *prog->p;
+  const size_t R = P.rules.size();
+  const size_t cells = (size_t)c->c->n * R;
+  D.kept_rules = -1;
+  HIPCHK(D.kept.ensure(cells));
+  // on the stream of the evaluation: after it, and before the corpus's next one (launch() keeps a
+  // corpus's launches ordered and a rebind waits for B.last)
+  hipStream_t s = B.last ? B.last : dev->stream;
+  if (cells) HIPCHK(hipMemcpyAsync(D.kept.p, B.verdicts.p, cells, hipMemcpyDeviceToDevice, s));
+  D.kept_names.assign(P.rule_names.begin(), P.rule_names.end());
+  D.kept_names.resize(R);
+  D.kept_rules = (int64_t)R;
+  return KPE_OK;
+}
+
+kpe_status kpe_results_drop(kpe_device* dev, kpe_corpus* c) {
+  if (!dev || !c) return fail(KPE_E_INVALID, "null argument");
+  if (!c->d) return KPE_OK;
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  kpe::DeviceCorpus& D = *c->d;
+  D.kept_rules = -1;
+  D.kept_names.clear();
+  if (D.kept.p) HIPCHK(hipFree(D.kept.p));  // waits for the copy
+  D.kept.p = nullptr, D.kept.bytes = 0;
+  return KPE_OK;
+}
+
+int kpe_results_kept_rules(const kpe_corpus* c) { return c && c->d ? (int)c->d->kept_rules : -1; }
+const char* kpe_results_kept_rule_name(const kpe_corpus* c, int r) {
+  if (!c || !c->d || r < 0 || r >= c->d->kept_rules) return nullptr;
+  return c->d->kept_names[(size_t)r].c_str();
+}
+
+kpe_status kpe_delta_column_map(const kpe_corpus* c, const kpe_program* prog, int32_t* old_of) {
+  if (!c || !prog) return fail(KPE_E_INVALID, "null argument");
+  if (!c->d || c->d->kept_rules < 0) return fail(KPE_E_STATE, "no kept result on this corpus");
+  const kpe::Program& P = *prog->p;
+  const size_t Rn = P.rules.size();
+  if (Rn && !old_of) return fail(KPE_E_INVALID, "null argument");
+  std::map<std::string, int32_t> kept;
+  for (size_t r = 0; r < c->d->kept_names.size(); ++r)
+    if (!kept.emplace(c->d->kept_names[r], (int32_t)r).second)
+      return fail(KPE_E_INVALID, "kept rule name occurs twice: " + c->d->kept_names[r]);
+  std::map<std::string, int32_t> seen;
+  for (size_t r = 0; r < Rn; ++r) {
+    const std::string name = r < P.rule_names.size() ? P.rule_names[r] : std::string();
+    if (!seen.emplace(name, (int32_t)r).second) return fail(KPE_E_INVALID, "rule name occurs twice: " + name);
+    const auto it = kept.find(name);
+    old_of[r] = it == kept.end() ? -1 : it->second;
+  }
+  return KPE_OK;
+}
+
+// The map's checks, shared by the device calls and the host twins: every entry is -1 or a kept
+// column, and no kept column is named twice. named[o] = 1 for the kept columns the map names.
+static kpe_status delta_map_check(const int32_t* old_of, size_t Rn, size_t Ro, std::vector<uint8_t>& named) {
+  named.assign(Ro, 0);
+  for (size_t r = 0; r < Rn; ++r) {
+    const int32_t o = old_of[r];
+    if (o == -1) continue;
+    if (o < -1 || (size_t)o >= Ro) return fail(KPE_E_INVALID, "column map entry outside the kept rules");
+    if (named[(size_t)o]) return fail(KPE_E_INVALID, "column map names a kept column twice");
+    named[(size_t)o] = 1;
+  }
+  return KPE_OK;
+}
+static inline bool delta_always(const uint8_t* always, size_t r, uint8_t x) {
+  return always && x < 8 && ((always[r] >> x) & 1);
+}
+
+int64_t kpe_changed_rows_host(const uint8_t* old_v, const uint8_t* new_v, uint64_t n, uint32_t Ro, uint32_t Rn,
+                              const int32_t* old_of, const uint8_t* always, uint64_t* rows, uint8_t* verdict_rows,
+                              uint64_t cap) {
+  if ((Rn && !old_of) || (cap && !rows)) return -(int64_t)fail(KPE_E_INVALID, "null argument");
+  if (n && ((Ro && !old_v) || (Rn && !new_v))) return -(int64_t)fail(KPE_E_INVALID, "null argument");
+  std::vector<uint8_t> named;
+  if (kpe_status st = delta_map_check(old_of, Rn, Ro, named)) return -(int64_t)st;
+  std::vector<uint32_t> gone;  // kept columns no entry names
+  for (uint32_t o = 0; o < Ro; ++o)
+    if (!named[o]) gone.push_back(o);
+  uint64_t total = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint8_t* nw = new_v + (size_t)i * Rn;
+    const uint8_t* od = old_v + (size_t)i * Ro;
+    bool ch = false;
+    for (uint32_t r = 0; r < Rn && !ch; ++r) {
+      const uint8_t x = nw[r], o = old_of[r] >= 0 ? od[old_of[r]] : (uint8_t)KPE_NA;
+      ch = x != o || delta_always(always, r, x);
+    }
+    for (size_t k = 0; k < gone.size() && !ch; ++k) ch = od[gone[k]] != KPE_NA;
+    if (!ch) continue;
+    if (total < cap) {
+      rows[total] = i;
+      if (verdict_rows && Rn) memcpy(verdict_rows + (size_t)total * Rn, nw, Rn);
+    }
+    ++total;
+  }
+  return (int64_t)total;
+}
+
+kpe_status kpe_delta_transitions_host(const uint8_t* old_v, const uint8_t* new_v, uint64_t n, uint32_t Ro, uint32_t Rn,
+                                      const int32_t* old_of, uint64_t* out) {
+  if (Rn && (!old_of || !out)) return fail(KPE_E_INVALID, "null argument");
+  if (n && ((Ro && !old_v) || (Rn && !new_v))) return fail(KPE_E_INVALID, "null argument");
+  std::vector<uint8_t> named;
+  if (kpe_status st = delta_map_check(old_of, Rn, Ro, named)) return st;
+  if (Rn) memset(out, 0, (size_t)Rn * 64 * sizeof(uint64_t));
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint8_t* nw = new_v + (size_t)i * Rn;
+    const uint8_t* od = old_v + (size_t)i * Ro;
+    for (uint32_t r = 0; r < Rn; ++r) {  // codes & 7: the alphabet
+      const uint32_t o = old_of[r] >= 0 ? od[old_of[r]] & 7u : (uint32_t)KPE_NA;
+      ++out[(size_t)r * 64 + o * 8 + (nw[r] & 7u)];
+    }
+  }
+  return KPE_OK;
+}
+
+// What kpe_changed_rows and kpe_delta_transitions check before any device call, and the tables
+// the kernels read: tab[r] = the kept column of new column r (bits 0-15, 0xFFFF: none) | always[r]
+// << 16; unm[o] = 1 for a kept column the map does not name.
+static kpe_status delta_tables(const kpe_program* prog, const kpe_corpus* c, const int32_t* old_of, const uint8_t* always,
+                               std::vector<uint32_t>& tab, std::vector<uint8_t>& unm, bool* any_unm) {
+  const char* const limit = "result deltas compare at most 4096 rules on either side";
+  const size_t Rn = prog->p->rules.size();
+  if (Rn > kpe_delta_max_rules()) return fail(KPE_E_LIMIT, limit);
+  if (!c->d || c->d->kept_rules < 0) return fail(KPE_E_STATE, "no kept result on this corpus");
+  const size_t Ro = (size_t)c->d->kept_rules;
+  if (Ro > kpe_delta_max_rules()) return fail(KPE_E_LIMIT, limit);
+  std::vector<int32_t> own;
+  if (!old_of) {
+    own.resize(std::max<size_t>(Rn, 1));
+    if (kpe_status st = kpe_delta_column_map(c, prog, own.data())) return st;
+    old_of = own.data();
+  }
+  if (kpe_status st = delta_map_check(old_of, Rn, Ro, unm)) return st;
+  *any_unm = false;
+  for (uint8_t& u : unm) {  // named -> unmapped
+    u = u ? 0 : 1;
+    *any_unm |= u != 0;
+  }
+  tab.resize(Rn);
+  for (size_t r = 0; r < Rn; ++r)
+    tab[r] = (old_of[r] < 0 ? 0xFFFFu : (uint32_t)old_of[r]) | ((uint32_t)(always ? always[r] : 0) << 16);
+  return KPE_OK;
+}
+// the binding checks of a query on the new matrix (under dev->mu)
+static kpe_status delta_bound(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c) {
+  HIPCHK(hipSetDevice(dev->ordinal));
+  if (c->d->bind.prog != prog->p.get()) return fail(KPE_E_STATE, "no evaluation of this program on this corpus");
+  if (c->d->ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  return KPE_OK;
+}
+
+static kpe_status changed_impl(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const int32_t* old_of,
+                               const uint8_t* always, uint64_t* rows_out, uint8_t* vrows_out, uint64_t cap,
+                               uint64_t* total_out) {
+  *total_out = 0;
+  if (!dev || !prog || !c) return fail(KPE_E_INVALID, "null argument");
+  if (cap && !rows_out) return fail(KPE_E_INVALID, "cap > 0 without a rows buffer");
+  std::vector<uint32_t> tab;
+  std::vector<uint8_t> unm;
+  bool any_unm = false;
+  if (kpe_status st = delta_tables(prog, c, old_of, always, tab, unm, &any_unm)) return st;
+  const size_t Rn = tab.size(), Ro = unm.size();
+  const uint64_t n = (uint64_t)c->c->n;
+  std::lock_guard<std::mutex> lk(dev->mu);
+  if (kpe_status st = delta_bound(dev, prog, c)) return st;
+  if (!n) return KPE_OK;
+  kpe::DeviceCorpus& D = *c->d;
+  auto& B = D.bind;
+  hipStream_t s = B.last ? B.last : dev->stream;
+  // scratch of this call (freed on every return path): the row flags as an N x 1 matrix for the
+  // selection chain, its tile offsets and counts, the tables
+  const uint64_t ntiles = (n + 4095u) / 4096u;
+  const size_t flag_bytes = (size_t)((n + 15u) & ~(uint64_t)15u);
+  const size_t off_bytes = (size_t)((ntiles + 2) & ~(uint64_t)1) * 8;
+  const size_t cnt_bytes = (size_t)((ntiles + 3) & ~(uint64_t)3) * 4;
+  const size_t tab_bytes = (Rn * 4 + 15u) & ~(size_t)15u;
+  DevBuf scratch, drows, dverd;
+  HIPCHK(scratch.ensure(flag_bytes + off_bytes + cnt_bytes + tab_bytes + Ro + 16));
+  uint8_t* base = scratch.as<uint8_t>();
+  uint8_t* d_flags = base;
+  uint64_t* d_off = reinterpret_cast<uint64_t*>(base + flag_bytes);
+  uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + flag_bytes + off_bytes);
+  uint32_t* d_tab = reinterpret_cast<uint32_t*>(base + flag_bytes + off_bytes + cnt_bytes);
+  uint8_t* d_sel = base + flag_bytes + off_bytes + cnt_bytes + tab_bytes;  // the flag matrix's one mask
+  uint8_t* d_unm = d_sel + 16;
+  const uint8_t sel1 = (uint8_t)KPE_SEL(1);
+  if (Rn) HIPCHK(hipMemcpyAsync(d_tab, tab.data(), Rn * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_sel, &sel1, 1, hipMemcpyHostToDevice, s));
+  if (any_unm) HIPCHK(hipMemcpyAsync(d_unm, unm.data(), Ro, hipMemcpyHostToDevice, s));
+  HIPCHK(kpe_launch_delta_flags(B.verdicts.as<uint8_t>(), D.kept.as<uint8_t>(), n, (uint32_t)Rn, (uint32_t)Ro, d_tab,
+                                any_unm ? d_unm : nullptr, d_flags, s));
+  HIPCHK(kpe_launch_select_count(d_flags, n, 1u, d_sel, 0, d_cnt, d_off, s));
+  uint64_t total = 0;
+  HIPCHK(hipMemcpyAsync(&total, d_off + ntiles, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *total_out = total;
+  const uint64_t m = std::min(total, cap);
+  if (!m) return KPE_OK;
+  HIPCHK(drows.ensure((size_t)m * 8));
+  HIPCHK(kpe_launch_select_scatter(d_flags, n, 1u, d_sel, 0, d_off, m, drows.as<uint64_t>(), nullptr, s));
+  const bool vr = vrows_out && Rn;
+  if (vr) {
+    HIPCHK(dverd.ensure((size_t)m * Rn));
+    HIPCHK(kpe_launch_gather_rows(B.verdicts.as<uint8_t>(), (uint32_t)Rn, drows.as<uint64_t>(), m, dverd.as<uint8_t>(), s));
+  }
+  HIPCHK(hipMemcpyAsync(rows_out, drows.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+  if (vr) HIPCHK(hipMemcpyAsync(vrows_out, dverd.p, (size_t)m * Rn, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return KPE_OK;
+}
+
+int64_t kpe_changed_rows(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const int32_t* old_of,
+                         const uint8_t* always, uint64_t* rows, uint8_t* verdict_rows, uint64_t cap) {
+  uint64_t total = 0;
+  const kpe_status st = changed_impl(dev, prog, c, old_of, always, rows, verdict_rows, cap, &total);
+  return st ? -(int64_t)st : (int64_t)total;
+}
+
+kpe_status kpe_delta_transitions(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const int32_t* old_of,
+                                 uint64_t* out) {
+  if (!dev || !prog || !c) return fail(KPE_E_INVALID, "null argument");
+  if (!out && prog->p->rules.size()) return fail(KPE_E_INVALID, "null argument");
+  std::vector<uint32_t> tab;
+  std::vector<uint8_t> unm;
+  bool any_unm = false;
+  if (kpe_status st = delta_tables(prog, c, old_of, nullptr, tab, unm, &any_unm)) return st;
+  const size_t Rn = tab.size(), Ro = unm.size();
+  std::lock_guard<std::mutex> lk(dev->mu);
+  if (kpe_status st = delta_bound(dev, prog, c)) return st;
+  if (!Rn) return KPE_OK;
+  kpe::DeviceCorpus& D = *c->d;
+  auto& B = D.bind;
+  hipStream_t s = B.last ? B.last : dev->stream;
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit counters");
+  const size_t out_bytes = Rn * 64 * sizeof(uint64_t);
+  DevBuf scratch;  // this call's: the tables' counters, then the map
+  HIPCHK(scratch.ensure(out_bytes + Rn * 4));
+  uint32_t* d_tab = reinterpret_cast<uint32_t*>(scratch.as<uint8_t>() + out_bytes);
+  HIPCHK(hipMemcpyAsync(d_tab, tab.data(), Rn * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(kpe_launch_delta_transitions(B.verdicts.as<uint8_t>(), D.kept.as<uint8_t>(), (uint64_t)c->c->n, (uint32_t)Rn,
+                                      (uint32_t)Ro, d_tab, scratch.as<unsigned long long>(), s));
   HIPCHK(hipMemcpyAsync(out, scratch.p, out_bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return KPE_OK;

@@ -5,6 +5,7 @@
 //  kpe_pack3_kernel      — the 3-bit verdict exchange.
 //  kpe_select_*_kernel, kpe_row_summary_kernel — sparse result fetch.
 //  kpe_ns_count*_kernel  — per-namespace rule counts.
+//  kpe_delta_*_kernel, kpe_gather_rows_kernel — result deltas against a kept matrix.
 // None of them reads a program or runs a VM.
 #include "kernels_common.h"
 
@@ -443,6 +444,141 @@ extern "C" hipError_t kpe_launch_row_summary(const uint8_t* v, uint32_t R, uint6
   else
     hipLaunchKernelGGL(kpe_row_summary_kernel<false>, grid, dim3(256), 0, s, v, R, row0, nrows, rpg, unscored, out);
   return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Result deltas (kpe_changed_rows, kpe_delta_transitions): the new verdict matrix of a resident
+// corpus against the one kpe_results_keep kept, column r of the new one against column tab[r] of
+// the kept one. The flag pass (delta.inl, shared with scripts/delta_check.cpp) writes one byte per
+// row; the row list is the selection chain above run over the flag bytes as an N x 1 matrix
+// (kpe_launch_select_count / _scatter with the mask KPE_SEL(1)); kpe_gather_rows_kernel copies the
+// listed rows. No global atomics on that path: a row's byte is written once, by the block that
+// owns the row's group.
+#define KPE_DELTA_FN __host__ __device__ __forceinline__
+#define KPE_DELTA_DEV __device__ __forceinline__
+namespace {
+__device__ __forceinline__ void delta_load16(const uint8_t* __restrict__ p, uint32_t cnt, uint32_t* w) {
+  const Cells16 c = load_cells(p, 0, cnt);
+  w[0] = c.w[0], w[1] = c.w[1], w[2] = c.w[2], w[3] = c.w[3];
+}
+__device__ __forceinline__ void delta_store16(uint8_t* p, const uint32_t* w) {
+  *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+#include "delta.inl"
+}  // namespace
+constexpr uint32_t kDeltaGrid = 2048;       // persistent blocks of the flag pass (8 per CU)
+constexpr uint32_t kDeltaTransRules = 192;  // rules per launch of the transition kernel: 64 words each, 48 KiB
+
+// All LDS is dynamic, so its base is 16-byte aligned for the staging stores (delta_lds).
+__global__ void __launch_bounds__(256) kpe_delta_flags_kernel(const uint8_t* __restrict__ vnew,
+                                                              const uint8_t* __restrict__ vold, uint64_t n, uint32_t Rn,
+                                                              uint32_t Ro, uint32_t rpg, const uint32_t* __restrict__ tab,
+                                                              const uint8_t* __restrict__ unmapped,
+                                                              uint8_t* __restrict__ flags) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_delta[];
+  const uint32_t t = threadIdx.x;
+  const DeltaLds L = delta_lds(Rn, Ro, rpg);
+  uint8_t* s_old = s_delta;
+  uint32_t* s_flag = reinterpret_cast<uint32_t*>(s_delta + L.flag_off);
+  uint32_t* s_tab = reinterpret_cast<uint32_t*>(s_delta + L.tab_off);
+  uint8_t* s_unm = s_delta + L.unm_off;
+  for (uint32_t i = t; i < Rn; i += 256u) s_tab[i] = tab[i];
+  if (unmapped)
+    for (uint32_t i = t; i < Ro; i += 256u) s_unm[i] = unmapped[i];
+  const uint64_t ngroups = (n + rpg - 1u) / rpg;
+  for (uint64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const DeltaGroup G = delta_group(g, n, Rn, Ro, rpg);
+    delta_stage(G, t, vold, s_old, s_flag);
+    __syncthreads();  // the first one also covers the tables
+    delta_compare(G, t, vnew, Rn, Ro, s_tab, s_old, s_flag);
+    if (unmapped) delta_sweep(G, t, Ro, s_unm, s_old, s_flag);  // uniform
+    __syncthreads();
+    delta_write(G, t, s_flag, flags);
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(256) kpe_gather_rows_kernel(const uint8_t* __restrict__ v, uint32_t R,
+                                                              const uint64_t* __restrict__ rows, uint64_t bytes,
+                                                              uint8_t* __restrict__ out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < bytes; i += (uint64_t)gridDim.x * 256u) {
+    const uint64_t k = i / R;
+    out[i] = v[rows[k] * R + (i - k * R)];
+  }
+}
+
+// Per new column r of [r0, r0 + rn) the 8 x 8 table of (kept code, new code) over all rows, after
+// kpe_count_kernel: a wave takes 64 rows at a time; per rule the lanes' (old, new) pairs are
+// counted with one ballot per distinct pair of the wave (a few), lane 0 accumulates in LDS; one
+// 64-bit global add per non-zero counter and block at the end. Codes are taken & 7 (the alphabet).
+__global__ void __launch_bounds__(256) kpe_delta_trans_kernel(const uint8_t* __restrict__ vnew,
+                                                              const uint8_t* __restrict__ vold, uint64_t n, uint32_t Rn,
+                                                              uint32_t Ro, const uint32_t* __restrict__ tab, uint32_t r0,
+                                                              uint32_t rn, unsigned long long* __restrict__ out) {
+  extern __shared__ uint32_t s_trans[];  // rules [r0, r0 + rn) x 64
+  const uint32_t t = threadIdx.x, lane = t & 63u;
+  for (uint32_t i = t; i < rn * 64u; i += 256u) s_trans[i] = 0u;
+  __syncthreads();
+  const uint64_t nw = (uint64_t)gridDim.x * 4u;
+  for (uint64_t tile = (uint64_t)blockIdx.x * 4u + (t >> 6); tile * 64u < n; tile += nw) {
+    const uint64_t row = tile * 64u + lane;
+    const bool live = row < n;
+    for (uint32_t r = 0; r < rn; ++r) {
+      const uint32_t m = tab[r0 + r] & 0xFFFFu;  // uniform
+      const uint32_t c = live ? vnew[row * Rn + r0 + r] & 7u : 0u;
+      const uint32_t o = live && m != kDeltaNone ? vold[row * Ro + m] & 7u : 0u;
+      const uint32_t key = o * 8u + c;
+      uint64_t rem = __ballot(live);  // uniform
+      while (rem) {
+        const uint32_t k = (uint32_t)__shfl((int)key, (int)__builtin_ctzll(rem), 64);
+        const uint64_t same = __ballot(live && key == k);
+        if (lane == 0) atomicAdd(&s_trans[r * 64u + k], (uint32_t)__popcll(same));
+        rem &= ~same;
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = t; i < rn * 64u; i += 256u)
+    if (s_trans[i]) atomicAdd(&out[(size_t)r0 * 64u + i], (unsigned long long)s_trans[i]);
+}
+
+extern "C" uint32_t kpe_delta_max_rules(void) { return kDeltaMaxRules; }
+extern "C" hipError_t kpe_launch_delta_flags(const uint8_t* vnew, const uint8_t* vold, uint64_t n, uint32_t Rn,
+                                             uint32_t Ro, const uint32_t* tab, const uint8_t* unmapped, uint8_t* flags,
+                                             hipStream_t s) {
+  if (!n) return hipSuccess;
+  if (Rn > kDeltaMaxRules || Ro > kDeltaMaxRules) return hipErrorInvalidValue;
+  const uint32_t rpg = delta_rows_per_group(Rn, Ro);
+  const uint64_t ngroups = (n + rpg - 1u) / rpg;
+  const dim3 grid((unsigned)std::min<uint64_t>(ngroups, kDeltaGrid));
+  hipLaunchKernelGGL(kpe_delta_flags_kernel, grid, dim3(256), (size_t)delta_lds(Rn, Ro, rpg).total, s, vnew, vold, n, Rn,
+                     Ro, rpg, tab, unmapped, flags);
+  return hipGetLastError();
+}
+extern "C" hipError_t kpe_launch_gather_rows(const uint8_t* v, uint32_t R, const uint64_t* rows, uint64_t nrows,
+                                             uint8_t* out, hipStream_t s) {
+  const uint64_t bytes = nrows * R;
+  if (!bytes) return hipSuccess;
+  const dim3 grid((unsigned)std::min<uint64_t>((bytes + 255u) / 256u, 1u << 20));
+  hipLaunchKernelGGL(kpe_gather_rows_kernel, grid, dim3(256), 0, s, v, R, rows, bytes, out);
+  return hipGetLastError();
+}
+extern "C" hipError_t kpe_launch_delta_transitions(const uint8_t* vnew, const uint8_t* vold, uint64_t n, uint32_t Rn,
+                                                   uint32_t Ro, const uint32_t* tab, unsigned long long* out,
+                                                   hipStream_t s) {
+  if (Rn == 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(out, 0, (size_t)Rn * 64 * 8, s);
+  if (e != hipSuccess || n == 0) return e;
+  const uint64_t waves = (n + 63u) / 64u;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((waves + 3u) / 4u, 1024);
+  for (uint32_t r0 = 0; r0 < Rn; r0 += kDeltaTransRules) {
+    const uint32_t rn = std::min<uint32_t>(kDeltaTransRules, Rn - r0);
+    hipLaunchKernelGGL(kpe_delta_trans_kernel, dim3(grid), dim3(256), (size_t)rn * 64 * 4, s, vnew, vold, n, Rn, Ro, tab,
+                       r0, rn, out);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 // ---------------------------------------------------------------------------

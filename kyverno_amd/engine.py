@@ -429,6 +429,71 @@ class Engine:
         check(load().kpe_fetch_namespace_counts(self.device.h, ps.h, corpus.h, g0, n, out.ctypes.data if n else None))
         return out
 
+    # ---- result deltas (a kept matrix per corpus, the rows that changed against it) ----
+    def keep_results(self, ps: PolicySet, corpus: Corpus):
+        """Keep the verdict matrix of the last evaluation of ps on corpus on the device
+        (kpe_results_keep: N x R bytes of HBM until drop_results or a re-upload), for changed_rows /
+        delta_transitions after the next evaluation."""
+        check(load().kpe_results_keep(self.device.h, ps.h, corpus.h))
+
+    def drop_results(self, corpus: Corpus):
+        check(load().kpe_results_drop(self.device.h, corpus.h))
+
+    def kept_rule_names(self, corpus: Corpus) -> Optional[List[str]]:
+        """The rule names of the kept result, or None when nothing is kept."""
+        L = load()
+        r = L.kpe_results_kept_rules(corpus.h)
+        return None if r < 0 else [L.kpe_results_kept_rule_name(corpus.h, i).decode() for i in range(r)]
+
+    def _delta_map(self, ps: PolicySet, column_map):
+        if column_map is None:
+            return None
+        m = np.ascontiguousarray(column_map, dtype=np.int32)
+        if m.shape != (ps.num_rules,):
+            raise ValueError("column_map: one entry per rule of ps")
+        return m if m.size else np.zeros(1, dtype=np.int32)
+
+    def changed_rows(self, ps: PolicySet, corpus: Corpus, column_map=None, always=0, cap: Optional[int] = None,
+                     with_verdicts=True):
+        """The rows of the last evaluation of ps on corpus that differ from the kept result
+        (kpe_changed_rows): (rows uint64 ascending, their verdict rows (k, R) uint8, total).
+        column_map: the kept column of each rule of ps or -1 (None: by rule name); always: a mask of
+        kpe_verdict bits (SEL(v)) per rule, or one for all: cells whose verdict is in it count as
+        changed. cap: at most that many rows come back; None: a count call, then one of that size."""
+        L = load()
+        R = ps.num_rules
+        mbuf = self._delta_map(ps, column_map)
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(always, dtype=np.uint8), (R,)) if np.ndim(always) == 0
+                                 else np.asarray(always, dtype=np.uint8))
+        if a.shape != (R,):
+            raise ValueError("always: one mask, or one per rule")
+        abuf = a if R else np.zeros(1, dtype=np.uint8)
+
+        def call(rows, vr, n):
+            t = L.kpe_changed_rows(self.device.h, ps.h, corpus.h, None if mbuf is None else mbuf.ctypes.data,
+                                   abuf.ctypes.data, rows.ctypes.data if n else None,
+                                   vr.ctypes.data if (vr is not None and n and R) else None, n)
+            if t < 0:
+                check(-t)
+            return int(t)
+
+        n = call(None, None, 0) if cap is None else min(int(cap), corpus.n)
+        rows = np.zeros(n, dtype=np.uint64)
+        vr = np.zeros((n, R), dtype=np.uint8) if with_verdicts else None
+        total = call(rows, vr, n) if (n or cap is not None) else 0
+        k = min(total, n)
+        return rows[:k], (vr[:k] if with_verdicts else np.zeros((0, R), dtype=np.uint8)), total
+
+    def delta_transitions(self, ps: PolicySet, corpus: Corpus, column_map=None) -> np.ndarray:
+        """Per rule of ps the 8 x 8 table [kept code, new code] of the corpus's rows
+        (kpe_delta_transitions): (R, 8, 8) uint64; the kept code is KPE_NA for an unmapped rule."""
+        R = ps.num_rules
+        mbuf = self._delta_map(ps, column_map)
+        out = np.zeros((R, 8, 8), dtype=np.uint64)
+        check(load().kpe_delta_transitions(self.device.h, ps.h, corpus.h, None if mbuf is None else mbuf.ctypes.data,
+                                           out.ctypes.data if R else None))
+        return out
+
     def pattern_traces(self, ps: PolicySet, corpus: Corpus, cells) -> np.ndarray:
         """Failing-path records of pattern cells (kpe_pattern_traces) after an evaluation of ps on
         corpus: cells = flat indices row * R + column; returns (len(cells), KPE_TRACE_ROOTS,
@@ -591,6 +656,71 @@ def row_summaries(ps: PolicySet, verdicts) -> np.ndarray:
     out = np.zeros((v.shape[0], 6), dtype=np.uint16)
     check(load().kpe_row_summaries_host(ps.h, v.ctypes.data if v.size else None, v.shape[0] if R else 0,
                                         out.ctypes.data if v.shape[0] else None))
+    return out
+
+
+def column_map(old_names: Sequence[str], new_names: Sequence[str]) -> np.ndarray:
+    """The map kpe_delta_column_map builds, from two lists of "<policy>/<rule>" names: for each
+    new rule the index of the old rule of the same name, or -1 (int32). A name that occurs twice
+    on either side is KPE_E_INVALID, as there."""
+    old = {}
+    for i, nm in enumerate(old_names):
+        if nm in old:
+            raise KpeError(1, f"kept rule name occurs twice: {nm}")
+        old[nm] = i
+    if len(set(new_names)) != len(new_names):
+        raise KpeError(1, "rule name occurs twice")
+    return np.array([old.get(nm, -1) for nm in new_names], dtype=np.int32)
+
+
+def _delta_args(Rn: int, cmap, always):
+    m = np.ascontiguousarray(cmap, dtype=np.int32)
+    if m.shape != (Rn,):
+        raise ValueError("column_map: one entry per new rule")
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(always, dtype=np.uint8), (Rn,)) if np.ndim(always) == 0
+                             else np.asarray(always, dtype=np.uint8))
+    if a.shape != (Rn,):
+        raise ValueError("always: one mask, or one per new rule")
+    # a valid address for Rn == 0
+    return (m if Rn else np.zeros(1, dtype=np.int32)), (a if Rn else np.zeros(1, dtype=np.uint8))
+
+
+def _delta_matrices(old, new):
+    o, v = np.ascontiguousarray(old, dtype=np.uint8), np.ascontiguousarray(new, dtype=np.uint8)
+    if o.ndim != 2 or v.ndim != 2 or o.shape[0] != v.shape[0]:
+        raise ValueError("old, new: verdict matrices of the same rows")
+    return o, v
+
+
+def changed_rows(old, new, column_map, always=0, cap: Optional[int] = None, with_verdicts=True):
+    """The rows of `new` (n, Rn) that differ from `old` (n, Ro) under column_map (kpe_changed_rows'
+    rule, through kpe_changed_rows_host; no device call): (rows uint64 ascending, their rows of
+    `new` (k, Rn) uint8, total). always: a mask of kpe_verdict bits (SEL(v)) per new rule, or one
+    for all; cap: at most that many rows come back."""
+    o, v = _delta_matrices(old, new)
+    n, Ro, Rn = v.shape[0], o.shape[1], v.shape[1]
+    m, a = _delta_args(Rn, column_map, always)
+    k = n if cap is None else min(int(cap), n)
+    rows = np.zeros(k, dtype=np.uint64)
+    vr = np.zeros((k, Rn), dtype=np.uint8) if with_verdicts else None
+    t = load().kpe_changed_rows_host(o.ctypes.data if o.size else None, v.ctypes.data if v.size else None, n, Ro, Rn,
+                                     m.ctypes.data, a.ctypes.data, rows.ctypes.data if k else None,
+                                     vr.ctypes.data if (vr is not None and vr.size) else None, k)
+    if t < 0:
+        check(-t)
+    k = min(int(t), k)
+    return rows[:k], (vr[:k] if with_verdicts else np.zeros((0, Rn), dtype=np.uint8)), int(t)
+
+
+def delta_transitions(old, new, column_map) -> np.ndarray:
+    """Per new rule the 8 x 8 table [old code, new code] of rows (kpe_delta_transitions_host; no
+    device call): (Rn, 8, 8) uint64; old is KPE_NA for a rule column_map maps to -1."""
+    o, v = _delta_matrices(old, new)
+    n, Ro, Rn = v.shape[0], o.shape[1], v.shape[1]
+    m, _ = _delta_args(Rn, column_map, 0)
+    out = np.zeros((Rn, 8, 8), dtype=np.uint64)
+    check(load().kpe_delta_transitions_host(o.ctypes.data if o.size else None, v.ctypes.data if v.size else None, n,
+                                            Ro, Rn, m.ctypes.data, out.ctypes.data if Rn else None))
     return out
 
 

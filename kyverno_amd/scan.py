@@ -15,7 +15,7 @@ import json
 import numpy as np
 
 from ._lib import KpeError, load
-from .engine import Corpus
+from .engine import SEL, Corpus
 
 
 def resource_hash(resource) -> str:
@@ -114,4 +114,47 @@ class BackgroundScanner:
         self._policy_token, self._ns_labels = policy_version, ns_labels
         self._policies, self._nrules = policies, R
         self.last_stats = {"rows": len(rows), "rescanned": len(dirty), "full": bool(full)}
+        return out
+
+
+class ResidentScanner:
+    """One corpus resident on the device, re-evaluated when the policies change; `apply` returns
+    only the rows whose report changes.
+
+    The background controller re-evaluates every resource after a policy or PolicyException change
+    and writes a report only when it differs from the stored one (pkg/controllers/report/
+    background/controller.go:379-419,463; ReportsAreIdentical, pkg/controllers/report/utils/
+    utils.go:66-88). Here the last result stays on the device (Engine.keep_results) and the
+    comparison runs there (Engine.changed_rows): the unchanged rows never cross to the host."""
+
+    MESSAGE_CODES = SEL(2) | SEL(4) | SEL(5)  # FAIL, ERROR, SKIP: results whose message the policy text decides
+
+    def __init__(self, engine, ndjson: bytes, ns_labels=None):
+        self.engine = engine
+        nsl = json.dumps(ns_labels).encode() if isinstance(ns_labels, dict) else ns_labels
+        self.corpus = Corpus(ndjson, nsl).upload(engine.device)
+        self._policies = None  # the PolicySet of the kept result (held while its matrix is kept)
+        self.last_stats = {}
+
+    def apply(self, policies, edited=()):
+        """Evaluate `policies` (a PolicySet) on the corpus and return {row: verdict row} of the rows
+        that differ from the last apply; the first call returns every row that has a response.
+        Rules are paired by "<policy>/<rule>" name. `edited` names policies whose text changed
+        under the same name: their FAIL / ERROR / SKIP cells count as changed whatever they were,
+        since the message may differ under an equal verdict."""
+        eng, corpus = self.engine, self.corpus
+        eng.evaluate_async(policies, corpus)
+        if self._policies is None:
+            v, _, _ = eng.fetch(policies, corpus)  # nothing to compare with: the whole matrix, once
+            out = {int(i): v[i].copy() for i in np.flatnonzero((v != 0).any(axis=1))}
+            total = len(out)
+        else:
+            names = set(edited)
+            always = np.array([self.MESSAGE_CODES if n.split("/", 1)[0] in names else 0 for n in policies.rule_names],
+                              dtype=np.uint8)
+            rows, vr, total = eng.changed_rows(policies, corpus, always=always)
+            out = {int(i): vr[k].copy() for k, i in enumerate(rows)}
+        eng.keep_results(policies, corpus)
+        self._policies = policies
+        self.last_stats = {"rows": corpus.n, "changed": total}
         return out
