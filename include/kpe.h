@@ -334,6 +334,86 @@ int64_t kpe_changed_rows_host(const uint8_t* old_v, const uint8_t* new_v, uint64
 kpe_status kpe_delta_transitions_host(const uint8_t* old_v, const uint8_t* new_v, uint64_t n, uint32_t Ro, uint32_t Rn,
                                       const int32_t* old_of, uint64_t* out);
 
+/* ---- row fingerprints -------------------------------------------------------- */
+/* Report-change detection in 8 bytes per resource. The reference decides "identical or not" from one
+ * small thing per report (ReportsAreIdentical, pkg/controllers/report/utils/utils.go:66-88) and stores
+ * the resource's hash as a label on it (pkg/utils/report/metadata.go:137-155). A fingerprint is the
+ * matching value of a resource's report results: the caller can store it with the report (an
+ * annotation), load it back after a restart or a re-upload, and compare on the device, so that only the
+ * changed rows come back. A kept matrix (kpe_results_keep) costs N x R bytes and dies with the upload;
+ * kept fingerprints cost 8 N bytes and can be restored.
+ *
+ * All arithmetic is on uint64_t and wraps.
+ *   mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ * (the splitmix64 finaliser: a bijection, mix64(0) == 0). For row i of an evaluation with R rules
+ *   fp(i) = sum over the columns r with v = V[i][r] != KPE_NA of
+ *             mix64( S(r, v) + 0x9E3779B97F4A7C15 * ( v | (uint64_t)m(i, r) << 8 ) )
+ *   S(r, v)  = msg_salts[r] when (msg_codes >> v) & 1, else salts[r]. msg_codes: one byte in the KPE_SEL
+ *              convention; KPE_SEL(KPE_FAIL) | KPE_SEL(KPE_ERROR) | KPE_SEL(KPE_SKIP) names the results
+ *              whose message the policy text decides. msg_salts == NULL means salts.
+ *   m(i, r)  = the cell's versioned-check mask word, bit 31 (KPE_CVM_XMATCH) included, exactly as
+ *              kpe_fetch_cv_masks returns it, when flags & KPE_FP_MASKS and v == KPE_FAIL; else 0. With
+ *              KPE_FP_MASKS the evaluation must have written masks (KPE_E_STATE otherwise, as
+ *              kpe_fetch_cv_masks).
+ * Properties:
+ *   - the sum commutes: a column permutation with its salts does not change fp;
+ *   - a column that is KPE_NA in the row contributes nothing: an added policy that does not match the
+ *     resource leaves its fingerprint, and its report, unchanged;
+ *   - fp == 0 for a row without responses (the controller's "no report");
+ *   - XOR a policy's resourceVersion (or an edit counter) into msg_salts[r] of its rules: an edit then
+ *     changes the fingerprint of exactly the rows with a msg_codes cell in those columns, the job
+ *     `always` does for kpe_changed_rows.
+ * A fingerprint is a hash: two different result sets of a row collide with probability 2^-64 per
+ * comparison. kpe_changed_rows against a kept matrix remains the exact form.
+ *
+ * More than KPE_DELTA_MAX_RULES rules is KPE_E_LIMIT for the device calls (checked before the state;
+ * the host twins have no limit). Argument checks come before any device call; the state rules are those
+ * of kpe_fetch_row_summaries. */
+#define KPE_FP_MASKS 1u
+/* salts[r] = mix64(FNV-1a-64("<policy>/<rule>")), 0 replaced by 1: the default salts, R entries. Host
+ * only. */
+kpe_status kpe_fp_rule_salts(const kpe_program* prog, uint64_t* salts);
+/* The fingerprints of rows [row0, row0 + nrows) of the last evaluation of prog on the corpus.
+ * salts == NULL: the default salts. KPE_E_INVALID when row0 + nrows > N, for a null argument or an
+ * unknown flag; nrows == 0 writes nothing. */
+kpe_status kpe_fetch_row_fingerprints(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c,
+                                      const uint64_t* salts, const uint64_t* msg_salts, uint8_t msg_codes,
+                                      uint32_t flags, uint64_t row0, uint64_t nrows, uint64_t* out);
+/* The same over nrows x R verdict bytes (and, with KPE_FP_MASKS, nrows x R mask words) the caller holds:
+ * the plain double loop, the specification of the device call, and what a caller without a resident
+ * corpus uses. salts is required; cv_masks may be NULL without KPE_FP_MASKS. Host only; no rule limit. */
+kpe_status kpe_row_fingerprints_host(uint32_t R, const uint8_t* verdicts, const uint32_t* cv_masks, uint64_t nrows,
+                                     const uint64_t* salts, const uint64_t* msg_salts, uint8_t msg_codes,
+                                     uint32_t flags, uint64_t* out);
+/* Compute the fingerprints of the last evaluation of prog on the corpus into an 8 x N byte buffer the
+ * corpus owns. Enqueued behind the evaluation, as kpe_results_keep is; does not wait. Kept fingerprints
+ * replace the previous ones and live until kpe_fingerprints_drop, kpe_corpus_upload or
+ * kpe_corpus_free; they are independent of the kept matrix, and both may exist at once. */
+kpe_status kpe_fingerprints_keep(kpe_device* dev, const kpe_program* prog, kpe_corpus* c, const uint64_t* salts,
+                                 const uint64_t* msg_salts, uint8_t msg_codes, uint32_t flags);
+/* Restore stored fingerprints as the kept ones (n must equal N: KPE_E_INVALID otherwise; KPE_E_STATE
+ * when the corpus is not uploaded to dev). */
+kpe_status kpe_fingerprints_load(kpe_device* dev, kpe_corpus* c, const uint64_t* fp, uint64_t n);
+/* Rows [row0, row0 + nrows) of the kept fingerprints (waits for a pending keep); KPE_E_STATE when
+ * nothing is kept. */
+kpe_status kpe_fingerprints_fetch(kpe_device* dev, const kpe_corpus* c, uint64_t row0, uint64_t nrows, uint64_t* out);
+kpe_status kpe_fingerprints_drop(kpe_device* dev, kpe_corpus* c);
+int kpe_fingerprints_kept(const kpe_corpus* c); /* 0 or 1 */
+/* The rows whose fingerprint under the last evaluation of prog differs from the kept one, ascending:
+ * the first min(total, cap) row indices into rows[], and, when not NULL, those rows of the new matrix
+ * (R bytes each) into verdict_rows[] and their new fingerprints into fps_out[]; memory past that is
+ * not written. rows == NULL with cap == 0 counts only. Returns the total, or -kpe_status: KPE_E_INVALID
+ * for a null argument, cap > 0 without rows or an unknown flag, KPE_E_LIMIT, then KPE_E_STATE when
+ * nothing is kept, the corpus has no evaluation of prog, or masks are asked for and were not written.
+ * The kept fingerprints are not modified: call kpe_fingerprints_keep to move on. */
+int64_t kpe_changed_rows_fp(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint64_t* salts,
+                            const uint64_t* msg_salts, uint8_t msg_codes, uint32_t flags, uint64_t* rows,
+                            uint8_t* verdict_rows, uint64_t* fps_out, uint64_t cap);
+/* The host twin of the comparison: the indices i < n with old_fp[i] != new_fp[i], same cap / count-only /
+ * return conventions. Host only. */
+int64_t kpe_changed_fingerprints_host(const uint64_t* old_fp, const uint64_t* new_fp, uint64_t n, uint64_t* rows,
+                                      uint64_t cap);
+
 /* ---- per-namespace rule counts ---------------------------------------------- */
 /* The verdict matrix reduced by namespace group on the device: per (group, rule) the cells of each
  * raw verdict code. `fail` counts KPE_FAIL cells whether or not the policy is scored, `warn`

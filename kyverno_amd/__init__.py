@@ -22,6 +22,9 @@ from .engine import (  # noqa: F401
     Device,
     Engine,
     EngineResponse,
+    FP_MASKS,
+    MESSAGE_CODES,
+    changed_fingerprints,
     changed_rows,
     column_map,
     delta_transitions,
@@ -36,7 +39,9 @@ from .engine import (  # noqa: F401
     cli_summary_ns,
     namespace_counts,
     report_results,
+    row_fingerprints,
     row_summaries,
+    rule_salts,
     synth_ns_labels,
     synth_resources,
 )
@@ -62,6 +67,9 @@ __all__ = [
     "changed_rows",
     "column_map",
     "delta_transitions",
+    "rule_salts",
+    "row_fingerprints",
+    "changed_fingerprints",
     "synth_ns_labels",
     "synth_resources",
     "load",

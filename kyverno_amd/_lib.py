@@ -108,6 +108,27 @@ def load():
     L.kpe_changed_rows_host.restype = i64
     L.kpe_delta_transitions_host.argtypes = [vp, vp, u64, u32, u32, vp, vp]
     L.kpe_delta_transitions_host.restype = ctypes.c_int
+    u8 = ctypes.c_uint8
+    L.kpe_fp_rule_salts.argtypes = [vp, vp]
+    L.kpe_fp_rule_salts.restype = ctypes.c_int
+    L.kpe_fetch_row_fingerprints.argtypes = [vp, vp, vp, vp, vp, u8, u32, u64, u64, vp]
+    L.kpe_fetch_row_fingerprints.restype = ctypes.c_int
+    L.kpe_row_fingerprints_host.argtypes = [u32, vp, vp, u64, vp, vp, u8, u32, vp]
+    L.kpe_row_fingerprints_host.restype = ctypes.c_int
+    L.kpe_fingerprints_keep.argtypes = [vp, vp, vp, vp, vp, u8, u32]
+    L.kpe_fingerprints_keep.restype = ctypes.c_int
+    L.kpe_fingerprints_load.argtypes = [vp, vp, vp, u64]
+    L.kpe_fingerprints_load.restype = ctypes.c_int
+    L.kpe_fingerprints_fetch.argtypes = [vp, vp, u64, u64, vp]
+    L.kpe_fingerprints_fetch.restype = ctypes.c_int
+    L.kpe_fingerprints_drop.argtypes = [vp, vp]
+    L.kpe_fingerprints_drop.restype = ctypes.c_int
+    L.kpe_fingerprints_kept.argtypes = [vp]
+    L.kpe_fingerprints_kept.restype = ctypes.c_int
+    L.kpe_changed_rows_fp.argtypes = [vp, vp, vp, vp, vp, u8, u32, vp, vp, vp, u64]
+    L.kpe_changed_rows_fp.restype = i64
+    L.kpe_changed_fingerprints_host.argtypes = [vp, vp, u64, vp, u64]
+    L.kpe_changed_fingerprints_host.restype = i64
     L.kpe_corpus_num_namespaces.argtypes = [vp]
     L.kpe_corpus_num_namespaces.restype = i64
     L.kpe_corpus_namespace.argtypes = [vp, i64]

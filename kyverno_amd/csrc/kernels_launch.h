@@ -73,4 +73,14 @@ hipError_t kpe_launch_gather_rows(const uint8_t* v, uint32_t R, const uint64_t* 
 hipError_t kpe_launch_delta_transitions(const uint8_t* vnew, const uint8_t* vold, uint64_t n, uint32_t Rn, uint32_t Ro,
                                         const uint32_t* tab, unsigned long long* out, hipStream_t s);
 uint32_t kpe_delta_max_rules(void);
+
+// row fingerprints (kpe_fetch_row_fingerprints, kpe_fingerprints_keep, kpe_changed_rows_fp). tbl:
+// 2 R words, [salts][msg_salts]; masks: the N x R cv mask words, or NULL when they do not count;
+// out: nrows words, row row0 + i at out[i], each written once. 1 <= R <= kpe_delta_max_rules().
+hipError_t kpe_launch_row_fp(const uint8_t* v, const uint32_t* masks, uint32_t R, uint64_t row0, uint64_t nrows,
+                             const uint64_t* tbl, uint32_t msg_codes, uint64_t* out, hipStream_t s);
+// flags[i] = a[i] != b[i], n bytes
+hipError_t kpe_launch_fp_diff(const uint64_t* a, const uint64_t* b, uint64_t n, uint8_t* flags, hipStream_t s);
+// out[i] = fp[rows[i]], m words
+hipError_t kpe_launch_fp_gather(const uint64_t* fp, const uint64_t* rows, uint64_t m, uint64_t* out, hipStream_t s);
 }

@@ -143,6 +143,10 @@ struct kpe_device {
   bool stage_busy[2] = {};
   int stage_cur = 0;
   double up_alloc_s = 0, up_copy_s = 0;  // KPE_DEBUG upload breakdown (under mu)
+  // kpe_changed_rows_fp's scratch (the new fingerprints, the row flags, the selection's tiles): 9
+  // bytes per row of the largest corpus compared so far, kept between calls (an allocation of
+  // that size costs more than the kernels). Used under mu by calls that wait before they return.
+  DevBuf fp_scratch;
   // kpe_fetch_namespace_counts with timing on: the last call's kernel time (HIP events) and the
   // last rows-by-namespace index build + upload (host clock)
   double ns_kernel_ms = 0, ns_index_ms = 0;
@@ -270,6 +274,10 @@ struct DeviceCorpus {
   DevBuf kept;
   int64_t kept_rules = -1;  // -1: nothing kept
   std::vector<std::string> kept_names;
+  // the kept fingerprints (kpe_fingerprints_keep / _load): 8 bytes per row, independent of `kept`
+  DevBuf fps;
+  std::vector<uint64_t> fps_tbl;  // host bytes of the last keep's salt table (its copy is enqueued)
+  bool fps_kept = false;
 };
 }  // namespace kpe
 
@@ -2510,6 +2518,282 @@ kpe_status kpe_delta_transitions(kpe_device* dev, const kpe_program* prog, const
   HIPCHK(hipMemcpyAsync(out, scratch.p, out_bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return KPE_OK;
+}
+
+// ---- row fingerprints: 8 bytes per row, kept per corpus, compared on the device -----------------
+static inline uint64_t fp_mix64(uint64_t z) {  // the splitmix64 finaliser
+  z ^= z >> 30;
+  z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27;
+  z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
+
+kpe_status kpe_fp_rule_salts(const kpe_program* prog, uint64_t* salts) {
+  if (!prog) return fail(KPE_E_INVALID, "null argument");
+  const kpe::Program& P = *prog->p;
+  const size_t R = P.rules.size();
+  if (R && !salts) return fail(KPE_E_INVALID, "null argument");
+  for (size_t r = 0; r < R; ++r) {
+    uint64_t h = 0xCBF29CE484222325ull;  // FNV-1a-64 of "<policy>/<rule>"
+    if (r < P.rule_names.size())
+      for (const unsigned char ch : P.rule_names[r]) h = (h ^ ch) * 0x100000001B3ull;
+    h = fp_mix64(h);
+    salts[r] = h ? h : 1;
+  }
+  return KPE_OK;
+}
+
+kpe_status kpe_row_fingerprints_host(uint32_t R, const uint8_t* verdicts, const uint32_t* cv_masks, uint64_t nrows,
+                                     const uint64_t* salts, const uint64_t* msg_salts, uint8_t msg_codes,
+                                     uint32_t flags, uint64_t* out) {
+  if (flags & ~KPE_FP_MASKS) return fail(KPE_E_INVALID, "unknown fingerprint flag");
+  if (nrows && !out) return fail(KPE_E_INVALID, "null argument");
+  const bool with_masks = (flags & KPE_FP_MASKS) != 0;
+  if (nrows && R && (!verdicts || !salts || (with_masks && !cv_masks))) return fail(KPE_E_INVALID, "null argument");
+  if (!msg_salts) msg_salts = salts;
+  for (uint64_t i = 0; i < nrows; ++i) {
+    uint64_t fp = 0;
+    for (uint32_t r = 0; r < R; ++r) {
+      const uint8_t v = verdicts[(size_t)i * R + r];
+      if (v == KPE_NA) continue;
+      const uint64_t s = v < 8 && ((msg_codes >> v) & 1) ? msg_salts[r] : salts[r];
+      const uint64_t m = with_masks && v == KPE_FAIL ? cv_masks[(size_t)i * R + r] : 0;
+      fp += fp_mix64(s + 0x9E3779B97F4A7C15ull * ((uint64_t)v | (m << 8)));
+    }
+    out[i] = fp;
+  }
+  return KPE_OK;
+}
+
+int64_t kpe_changed_fingerprints_host(const uint64_t* old_fp, const uint64_t* new_fp, uint64_t n, uint64_t* rows,
+                                      uint64_t cap) {
+  if (cap && !rows) return -(int64_t)fail(KPE_E_INVALID, "cap > 0 without a rows buffer");
+  if (n && (!old_fp || !new_fp)) return -(int64_t)fail(KPE_E_INVALID, "null argument");
+  uint64_t total = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (old_fp[i] == new_fp[i]) continue;
+    if (total < cap) rows[total] = i;
+    ++total;
+  }
+  return (int64_t)total;
+}
+
+// What the device calls check before any device call, and the table the kernel reads:
+// [salts: R][msg_salts: R].
+static kpe_status fp_table(const kpe_program* prog, const uint64_t* salts, const uint64_t* msg_salts, uint32_t flags,
+                           std::vector<uint64_t>& tbl) {
+  if (flags & ~KPE_FP_MASKS) return fail(KPE_E_INVALID, "unknown fingerprint flag");
+  const size_t R = prog->p->rules.size();
+  if (R > kpe_delta_max_rules()) return fail(KPE_E_LIMIT, "row fingerprints take at most 4096 rules");
+  tbl.resize(2 * R);
+  if (!R) return KPE_OK;
+  if (salts) memcpy(tbl.data(), salts, R * 8);
+  else if (kpe_status st = kpe_fp_rule_salts(prog, tbl.data())) return st;
+  memcpy(tbl.data() + R, msg_salts ? msg_salts : tbl.data(), R * 8);
+  return KPE_OK;
+}
+// The binding checks of a fingerprint query (under dev->mu), and the launch: rows [row0, row0 +
+// nrows) into d_out, the table copied from h_tbl (which must live until the copy ran) to d_tbl.
+static kpe_status fp_compute(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint64_t* h_tbl,
+                             uint8_t msg_codes, uint32_t flags, uint64_t row0, uint64_t nrows, uint64_t* d_tbl,
+                             uint64_t* d_out, hipStream_t s) {
+  const size_t R = prog->p->rules.size();
+  if (!nrows) return KPE_OK;
+  if (!R) {
+    HIPCHK(hipMemsetAsync(d_out, 0, (size_t)nrows * 8, s));
+    return KPE_OK;
+  }
+  auto& B = c->d->bind;
+  const uint32_t* d_masks = (flags & KPE_FP_MASKS) ? B.masks.as<uint32_t>() : nullptr;
+  HIPCHK(hipMemcpyAsync(d_tbl, h_tbl, R * 16, hipMemcpyHostToDevice, s));
+  HIPCHK(kpe_launch_row_fp(B.verdicts.as<uint8_t>(), d_masks, (uint32_t)R, row0, nrows, d_tbl, msg_codes, d_out, s));
+  return KPE_OK;
+}
+static kpe_status fp_bound(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, uint32_t flags) {
+  if (!c->d) return fail(KPE_E_STATE, "corpus not uploaded");
+  if (kpe_status st = delta_bound(dev, prog, c)) return st;
+  // the kernel reads a word per FAIL cell: the buffer must hold this program's N x R words
+  const size_t cells = (size_t)c->c->n * prog->p->rules.size();
+  if ((flags & KPE_FP_MASKS) && (!c->d->has_masks || c->d->bind.masks.bytes < cells * 4))
+    return fail(KPE_E_STATE, "check masks were not computed");
+  return KPE_OK;
+}
+
+kpe_status kpe_fetch_row_fingerprints(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c,
+                                      const uint64_t* salts, const uint64_t* msg_salts, uint8_t msg_codes,
+                                      uint32_t flags, uint64_t row0, uint64_t nrows, uint64_t* out) {
+  if (!dev || !prog || !c || (nrows && !out)) return fail(KPE_E_INVALID, "null argument");
+  std::vector<uint64_t> tbl;
+  if (kpe_status st = fp_table(prog, salts, msg_salts, flags, tbl)) return st;
+  if (row0 > (uint64_t)c->c->n || nrows > (uint64_t)c->c->n - row0) return fail(KPE_E_INVALID, "rows past the corpus");
+  if (!nrows) return KPE_OK;
+  const size_t R = tbl.size() / 2;
+  if (!R) {
+    memset(out, 0, nrows * 8);
+    return KPE_OK;
+  }
+  if (!c->d) return fail(KPE_E_STATE, "corpus not uploaded");
+  std::lock_guard<std::mutex> lk(dev->mu);
+  if (kpe_status st = fp_bound(dev, prog, c, flags)) return st;
+  auto& B = c->d->bind;
+  hipStream_t s = B.last ? B.last : dev->stream;
+  const size_t out_bytes = (size_t)nrows * 8;
+  DevBuf scratch;  // this call's: the rows' fingerprints, then the table
+  HIPCHK(scratch.ensure(out_bytes + R * 16));
+  uint64_t* d_tbl = scratch.as<uint64_t>() + nrows;
+  if (kpe_status st = fp_compute(dev, prog, c, tbl.data(), msg_codes, flags, row0, nrows, d_tbl, scratch.as<uint64_t>(), s))
+    return st;
+  HIPCHK(hipMemcpyAsync(out, scratch.p, out_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return KPE_OK;
+}
+
+kpe_status kpe_fingerprints_keep(kpe_device* dev, const kpe_program* prog, kpe_corpus* c, const uint64_t* salts,
+                                 const uint64_t* msg_salts, uint8_t msg_codes, uint32_t flags) {
+  if (!dev || !prog || !c) return fail(KPE_E_INVALID, "null argument");
+  std::vector<uint64_t> tbl;
+  if (kpe_status st = fp_table(prog, salts, msg_salts, flags, tbl)) return st;
+  if (!c->d) return fail(KPE_E_STATE, "corpus not uploaded");
+  std::lock_guard<std::mutex> lk(dev->mu);
+  if (kpe_status st = fp_bound(dev, prog, c, flags)) return st;
+  kpe::DeviceCorpus& D = *c->d;
+  const uint64_t n = (uint64_t)c->c->n;
+  const size_t R = tbl.size() / 2;
+  D.fps_kept = false;
+  HIPCHK(D.fps.ensure((size_t)n * 8 + R * 16));  // the fingerprints, then the table
+  // the table's copy is enqueued, not waited for: its host bytes belong to the corpus
+  D.fps_tbl.swap(tbl);
+  hipStream_t s = D.bind.last ? D.bind.last : dev->stream;
+  if (kpe_status st = fp_compute(dev, prog, c, D.fps_tbl.data(), msg_codes, flags, 0, n, D.fps.as<uint64_t>() + n,
+                                 D.fps.as<uint64_t>(), s))
+    return st;
+  D.fps_kept = true;
+  return KPE_OK;
+}
+
+kpe_status kpe_fingerprints_load(kpe_device* dev, kpe_corpus* c, const uint64_t* fp, uint64_t n) {
+  if (!dev || !c || (n && !fp)) return fail(KPE_E_INVALID, "null argument");
+  if (n != (uint64_t)c->c->n) return fail(KPE_E_INVALID, "one fingerprint per row of the corpus");
+  if (!c->d) return fail(KPE_E_STATE, "corpus not uploaded");
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  kpe::DeviceCorpus& D = *c->d;
+  if (D.ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  D.fps_kept = false;
+  HIPCHK(D.fps.ensure((size_t)n * 8));
+  hipStream_t s = D.bind.last ? D.bind.last : dev->stream;
+  if (n) {
+    HIPCHK(hipMemcpyAsync(D.fps.p, fp, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));  // fp is the caller's
+  }
+  D.fps_kept = true;
+  return KPE_OK;
+}
+
+kpe_status kpe_fingerprints_fetch(kpe_device* dev, const kpe_corpus* c, uint64_t row0, uint64_t nrows, uint64_t* out) {
+  if (!dev || !c || (nrows && !out)) return fail(KPE_E_INVALID, "null argument");
+  if (row0 > (uint64_t)c->c->n || nrows > (uint64_t)c->c->n - row0) return fail(KPE_E_INVALID, "rows past the corpus");
+  if (!c->d || !c->d->fps_kept) return fail(KPE_E_STATE, "no kept fingerprints on this corpus");
+  if (!nrows) return KPE_OK;
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  const kpe::DeviceCorpus& D = *c->d;
+  if (D.ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  hipStream_t s = D.bind.last ? D.bind.last : dev->stream;
+  HIPCHK(hipMemcpyAsync(out, D.fps.as<uint64_t>() + row0, (size_t)nrows * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return KPE_OK;
+}
+
+kpe_status kpe_fingerprints_drop(kpe_device* dev, kpe_corpus* c) {
+  if (!dev || !c) return fail(KPE_E_INVALID, "null argument");
+  if (!c->d) return KPE_OK;
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  kpe::DeviceCorpus& D = *c->d;
+  D.fps_kept = false;
+  if (D.fps.p) HIPCHK(hipFree(D.fps.p));  // waits for a pending keep
+  D.fps.p = nullptr, D.fps.bytes = 0;
+  return KPE_OK;
+}
+
+int kpe_fingerprints_kept(const kpe_corpus* c) { return c && c->d && c->d->fps_kept ? 1 : 0; }
+
+static kpe_status changed_fp_impl(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint64_t* salts,
+                                  const uint64_t* msg_salts, uint8_t msg_codes, uint32_t flags, uint64_t* rows_out,
+                                  uint8_t* vrows_out, uint64_t* fps_out, uint64_t cap, uint64_t* total_out) {
+  *total_out = 0;
+  if (!dev || !prog || !c) return fail(KPE_E_INVALID, "null argument");
+  if (cap && !rows_out) return fail(KPE_E_INVALID, "cap > 0 without a rows buffer");
+  std::vector<uint64_t> tbl;
+  if (kpe_status st = fp_table(prog, salts, msg_salts, flags, tbl)) return st;
+  if (!c->d || !c->d->fps_kept) return fail(KPE_E_STATE, "no kept fingerprints on this corpus");
+  const size_t R = tbl.size() / 2;
+  const uint64_t n = (uint64_t)c->c->n;
+  std::lock_guard<std::mutex> lk(dev->mu);
+  if (kpe_status st = fp_bound(dev, prog, c, flags)) return st;
+  if (!n) return KPE_OK;
+  kpe::DeviceCorpus& D = *c->d;
+  auto& B = D.bind;
+  hipStream_t s = B.last ? B.last : dev->stream;
+  // the device's scratch: the new fingerprints, the row flags as an N x 1 matrix for the selection
+  // chain, its tile offsets and counts, its one mask, the table
+  const uint64_t ntiles = (n + 4095u) / 4096u;
+  const size_t fp_bytes = (size_t)((n + 1u) & ~(uint64_t)1u) * 8;
+  const size_t flag_bytes = (size_t)((n + 15u) & ~(uint64_t)15u);
+  const size_t off_bytes = (size_t)((ntiles + 2) & ~(uint64_t)1) * 8;
+  const size_t cnt_bytes = (size_t)((ntiles + 3) & ~(uint64_t)3) * 4;
+  DevBuf& scratch = dev->fp_scratch;
+  DevBuf drows, dverd, dfps;
+  HIPCHK(scratch.ensure(fp_bytes + flag_bytes + off_bytes + cnt_bytes + 16 + R * 16));
+  uint8_t* base = scratch.as<uint8_t>();
+  uint64_t* d_new = reinterpret_cast<uint64_t*>(base);
+  uint8_t* d_flags = base + fp_bytes;
+  uint64_t* d_off = reinterpret_cast<uint64_t*>(base + fp_bytes + flag_bytes);
+  uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + fp_bytes + flag_bytes + off_bytes);
+  uint8_t* d_sel = base + fp_bytes + flag_bytes + off_bytes + cnt_bytes;
+  uint64_t* d_tbl = reinterpret_cast<uint64_t*>(d_sel + 16);
+  const uint8_t sel1 = (uint8_t)KPE_SEL(1);
+  HIPCHK(hipMemcpyAsync(d_sel, &sel1, 1, hipMemcpyHostToDevice, s));
+  if (kpe_status st = fp_compute(dev, prog, c, tbl.data(), msg_codes, flags, 0, n, d_tbl, d_new, s)) {
+    (void)hipStreamSynchronize(s);
+    return st;
+  }
+  HIPCHK(kpe_launch_fp_diff(d_new, D.fps.as<uint64_t>(), n, d_flags, s));
+  HIPCHK(kpe_launch_select_count(d_flags, n, 1u, d_sel, 0, d_cnt, d_off, s));
+  uint64_t total = 0;
+  HIPCHK(hipMemcpyAsync(&total, d_off + ntiles, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *total_out = total;
+  const uint64_t m = std::min(total, cap);
+  if (!m) return KPE_OK;
+  HIPCHK(drows.ensure((size_t)m * 8));
+  HIPCHK(kpe_launch_select_scatter(d_flags, n, 1u, d_sel, 0, d_off, m, drows.as<uint64_t>(), nullptr, s));
+  const bool vr = vrows_out && R;
+  if (vr) {
+    HIPCHK(dverd.ensure((size_t)m * R));
+    HIPCHK(kpe_launch_gather_rows(B.verdicts.as<uint8_t>(), (uint32_t)R, drows.as<uint64_t>(), m, dverd.as<uint8_t>(), s));
+  }
+  if (fps_out) {
+    HIPCHK(dfps.ensure((size_t)m * 8));
+    HIPCHK(kpe_launch_fp_gather(d_new, drows.as<uint64_t>(), m, dfps.as<uint64_t>(), s));
+  }
+  HIPCHK(hipMemcpyAsync(rows_out, drows.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+  if (vr) HIPCHK(hipMemcpyAsync(vrows_out, dverd.p, (size_t)m * R, hipMemcpyDeviceToHost, s));
+  if (fps_out) HIPCHK(hipMemcpyAsync(fps_out, dfps.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return KPE_OK;
+}
+
+int64_t kpe_changed_rows_fp(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint64_t* salts,
+                            const uint64_t* msg_salts, uint8_t msg_codes, uint32_t flags, uint64_t* rows,
+                            uint8_t* verdict_rows, uint64_t* fps_out, uint64_t cap) {
+  uint64_t total = 0;
+  const kpe_status st =
+      changed_fp_impl(dev, prog, c, salts, msg_salts, msg_codes, flags, rows, verdict_rows, fps_out, cap, &total);
+  return st ? -(int64_t)st : (int64_t)total;
 }
 
 // ---- namespace groups and per-namespace rule counts -------------------------------------------

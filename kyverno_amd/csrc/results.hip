@@ -6,6 +6,7 @@
 //  kpe_select_*_kernel, kpe_row_summary_kernel — sparse result fetch.
 //  kpe_ns_count*_kernel  — per-namespace rule counts.
 //  kpe_delta_*_kernel, kpe_gather_rows_kernel — result deltas against a kept matrix.
+//  kpe_row_fp_kernel, kpe_fp_diff_kernel, kpe_fp_gather_kernel — row fingerprints and their compare.
 // None of them reads a program or runs a VM.
 #include "kernels_common.h"
 
@@ -579,6 +580,99 @@ extern "C" hipError_t kpe_launch_delta_transitions(const uint8_t* vnew, const ui
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------
+// Row fingerprints (kpe_fetch_row_fingerprints, kpe_fingerprints_keep, kpe_changed_rows_fp): 8 bytes
+// per row, the shape of kpe_row_summary_kernel (fp.inl, shared with scripts/fp_check.cpp). The
+// changed rows are kpe_fp_diff_kernel's byte per row through the selection chain as an N x 1
+// matrix, like the delta flags; kpe_gather_rows_kernel and kpe_fp_gather_kernel copy what the
+// listed rows need. No global atomics, no zeroing pass: a row's word is written once.
+#define KPE_FP_FN __host__ __device__ __forceinline__
+#define KPE_FP_DEV __device__ __forceinline__
+namespace {
+__device__ __forceinline__ void fp_load16(const uint8_t* __restrict__ p, uint32_t cnt, uint32_t* w) {
+  const Cells16 c = load_cells(p, 0, cnt);
+  w[0] = c.w[0], w[1] = c.w[1], w[2] = c.w[2], w[3] = c.w[3];
+}
+__device__ __forceinline__ void fp_lds_add(uint64_t* p, uint64_t x) {
+  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)x);
+}
+#include "fp.inl"
+}  // namespace
+constexpr uint32_t kFpGrid = 2048;  // persistent blocks (8 per CU where the LDS allows)
+
+// tbl: [salts: R][msg_salts: R]. LDS: both tables staged in dynamic LDS (R <= kFpLdsRules); MASKS:
+// the FAIL cells' mask words count (the verdict-only instance has no such load).
+template <bool LDS, bool MASKS>
+__global__ void __launch_bounds__(256) kpe_row_fp_kernel(const uint8_t* __restrict__ v, const uint32_t* __restrict__ masks,
+                                                         uint32_t R, uint64_t row0, uint64_t nrows, uint32_t rpg,
+                                                         const uint64_t* __restrict__ tbl_g, uint32_t msg_codes,
+                                                         uint64_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_fp_dyn[];
+  __shared__ uint64_t s_fp[kFpMaxRows];
+  const uint32_t t = threadIdx.x;
+  const uint64_t* tbl = tbl_g;
+  if (LDS) {  // the first barrier of the loop covers the staging
+    uint64_t* l = reinterpret_cast<uint64_t*>(s_fp_dyn);
+    for (uint32_t i = t; i < 2u * R; i += 256u) l[i] = tbl_g[i];
+    tbl = l;
+  }
+  const uint64_t ngroups = (nrows + rpg - 1u) / rpg;
+  for (uint64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const FpGroup G = fp_group(g, row0, nrows, R, rpg);
+    fp_clear(G, t, s_fp);
+    __syncthreads();
+    fp_accum<MASKS>(G, t, v, masks, R, tbl, msg_codes, s_fp);
+    __syncthreads();
+    fp_write(G, t, s_fp, out);
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(256) kpe_fp_diff_kernel(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b,
+                                                          uint64_t n, uint8_t* __restrict__ flags) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
+    flags[i] = a[i] != b[i] ? 1u : 0u;
+}
+__global__ void __launch_bounds__(256) kpe_fp_gather_kernel(const uint64_t* __restrict__ fp,
+                                                            const uint64_t* __restrict__ rows, uint64_t m,
+                                                            uint64_t* __restrict__ out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < m; i += (uint64_t)gridDim.x * 256u)
+    out[i] = fp[rows[i]];
+}
+
+extern "C" hipError_t kpe_launch_row_fp(const uint8_t* v, const uint32_t* masks, uint32_t R, uint64_t row0,
+                                        uint64_t nrows, const uint64_t* tbl, uint32_t msg_codes, uint64_t* out,
+                                        hipStream_t s) {
+  if (!nrows) return hipSuccess;
+  if (!R || R > kFpMaxRules) return hipErrorInvalidValue;
+  const uint32_t rpg = fp_rows_per_group(R);
+  const uint64_t ngroups = (nrows + rpg - 1u) / rpg;
+  const dim3 grid((unsigned)std::min<uint64_t>(ngroups, kFpGrid));
+  const bool lds = R <= kFpLdsRules;
+  const size_t dyn = lds ? (size_t)R * 16u : 0u;
+#define KPE_FP_LAUNCH(L, M) \
+  hipLaunchKernelGGL((kpe_row_fp_kernel<L, M>), grid, dim3(256), dyn, s, v, masks, R, row0, nrows, rpg, tbl, msg_codes, out)
+  if (lds && masks) KPE_FP_LAUNCH(true, true);
+  else if (lds) KPE_FP_LAUNCH(true, false);
+  else if (masks) KPE_FP_LAUNCH(false, true);
+  else KPE_FP_LAUNCH(false, false);
+#undef KPE_FP_LAUNCH
+  return hipGetLastError();
+}
+extern "C" hipError_t kpe_launch_fp_diff(const uint64_t* a, const uint64_t* b, uint64_t n, uint8_t* flags, hipStream_t s) {
+  if (!n) return hipSuccess;
+  const dim3 grid((unsigned)std::min<uint64_t>((n + 255u) / 256u, 1u << 16));
+  hipLaunchKernelGGL(kpe_fp_diff_kernel, grid, dim3(256), 0, s, a, b, n, flags);
+  return hipGetLastError();
+}
+extern "C" hipError_t kpe_launch_fp_gather(const uint64_t* fp, const uint64_t* rows, uint64_t m, uint64_t* out,
+                                           hipStream_t s) {
+  if (!m) return hipSuccess;
+  const dim3 grid((unsigned)std::min<uint64_t>((m + 255u) / 256u, 1u << 16));
+  hipLaunchKernelGGL(kpe_fp_gather_kernel, grid, dim3(256), 0, s, fp, rows, m, out);
+  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------

@@ -494,6 +494,76 @@ class Engine:
                                            out.ctypes.data if R else None))
         return out
 
+    # ---- row fingerprints (8 bytes per row: kept, stored by the caller, compared on the device) ----
+    def row_fingerprints(self, ps: PolicySet, corpus: Corpus, salts=None, msg_salts=None, msg_codes=None, masks=False,
+                         row0: int = 0, nrows: Optional[int] = None) -> np.ndarray:
+        """The fingerprints of rows [row0, row0 + nrows) of the last evaluation of ps on corpus
+        (kpe_fetch_row_fingerprints): (nrows,) uint64. salts: one per rule (None: rule_salts(ps));
+        msg_salts: the salts of the cells whose verdict is in msg_codes (None: salts; msg_codes None:
+        MESSAGE_CODES); masks: FAIL cells' check mask words count (the evaluation wrote masks)."""
+        n = corpus.n - row0 if nrows is None else nrows
+        s, ms, mc = _fp_salts(ps.num_rules, salts, msg_salts, msg_codes)
+        out = np.zeros(max(n, 0), dtype=np.uint64)
+        check(load().kpe_fetch_row_fingerprints(self.device.h, ps.h, corpus.h, _ptr(s), _ptr(ms), mc,
+                                                FP_MASKS if masks else 0, row0, n, out.ctypes.data if n > 0 else None))
+        return out
+
+    def keep_fingerprints(self, ps: PolicySet, corpus: Corpus, salts=None, msg_salts=None, msg_codes=None, masks=False):
+        """Keep the fingerprints of the last evaluation of ps on corpus on the device
+        (kpe_fingerprints_keep: 8 N bytes of HBM until drop_fingerprints or a re-upload), for
+        changed_rows_fp after the next evaluation. Arguments as row_fingerprints."""
+        s, ms, mc = _fp_salts(ps.num_rules, salts, msg_salts, msg_codes)
+        check(load().kpe_fingerprints_keep(self.device.h, ps.h, corpus.h, _ptr(s), _ptr(ms), mc, FP_MASKS if masks else 0))
+
+    def load_fingerprints(self, corpus: Corpus, fingerprints):
+        """Restore stored fingerprints, one per row of corpus, as the kept ones (kpe_fingerprints_load)."""
+        fp = np.ascontiguousarray(fingerprints, dtype=np.uint64)
+        if fp.ndim != 1:
+            raise ValueError("fingerprints: one uint64 per row")
+        check(load().kpe_fingerprints_load(self.device.h, corpus.h, fp.ctypes.data if fp.size else None, fp.size))
+
+    def kept_fingerprints(self, corpus: Corpus, row0: int = 0, nrows: Optional[int] = None) -> Optional[np.ndarray]:
+        """The kept fingerprints of rows [row0, row0 + nrows) (kpe_fingerprints_fetch), or None when
+        nothing is kept: what a caller stores with the reports."""
+        L = load()
+        if not L.kpe_fingerprints_kept(corpus.h):
+            return None
+        n = corpus.n - row0 if nrows is None else nrows
+        out = np.zeros(max(n, 0), dtype=np.uint64)
+        check(L.kpe_fingerprints_fetch(self.device.h, corpus.h, row0, n, out.ctypes.data if n > 0 else None))
+        return out
+
+    def drop_fingerprints(self, corpus: Corpus):
+        check(load().kpe_fingerprints_drop(self.device.h, corpus.h))
+
+    def changed_rows_fp(self, ps: PolicySet, corpus: Corpus, salts=None, msg_salts=None, msg_codes=None, masks=False,
+                        cap: Optional[int] = None, with_verdicts=True):
+        """The rows whose fingerprint under the last evaluation of ps on corpus differs from the
+        kept one (kpe_changed_rows_fp): (rows uint64 ascending, their verdict rows (k, R) uint8,
+        their new fingerprints (k,) uint64, total). The kept fingerprints stay as they are. cap: at
+        most that many rows come back; None: a count call, then one of that size."""
+        L = load()
+        R = ps.num_rules
+        s, ms, mc = _fp_salts(R, salts, msg_salts, msg_codes)
+        fl = FP_MASKS if masks else 0
+
+        def call(rows, vr, fps, n):
+            t = L.kpe_changed_rows_fp(self.device.h, ps.h, corpus.h, _ptr(s), _ptr(ms), mc, fl,
+                                      rows.ctypes.data if n else None,
+                                      vr.ctypes.data if (vr is not None and n and R) else None,
+                                      fps.ctypes.data if n else None, n)
+            if t < 0:
+                check(-t)
+            return int(t)
+
+        n = call(None, None, None, 0) if cap is None else min(int(cap), corpus.n)
+        rows = np.zeros(n, dtype=np.uint64)
+        fps = np.zeros(n, dtype=np.uint64)
+        vr = np.zeros((n, R), dtype=np.uint8) if with_verdicts else None
+        total = call(rows, vr, fps, n) if (n or cap is not None) else 0
+        k = min(total, n)
+        return rows[:k], (vr[:k] if with_verdicts else np.zeros((0, R), dtype=np.uint8)), fps[:k], total
+
     def pattern_traces(self, ps: PolicySet, corpus: Corpus, cells) -> np.ndarray:
         """Failing-path records of pattern cells (kpe_pattern_traces) after an evaluation of ps on
         corpus: cells = flat indices row * R + column; returns (len(cells), KPE_TRACE_ROOTS,
@@ -722,6 +792,78 @@ def delta_transitions(old, new, column_map) -> np.ndarray:
     check(load().kpe_delta_transitions_host(o.ctypes.data if o.size else None, v.ctypes.data if v.size else None, n,
                                             Ro, Rn, m.ctypes.data, out.ctypes.data if Rn else None))
     return out
+
+
+FP_MASKS = 1  # include/kpe.h KPE_FP_MASKS: FAIL cells' check mask words count
+MESSAGE_CODES = SEL(2) | SEL(4) | SEL(5)  # FAIL, ERROR, SKIP: results whose message the policy text decides
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _fp_salts(R: int, salts, msg_salts, msg_codes):
+    """(salts or None, msg_salts or None, msg_codes) as the C calls take them."""
+    def one(x, what):
+        if x is None:
+            return None
+        a = np.ascontiguousarray(x, dtype=np.uint64)
+        if a.shape != (R,):
+            raise ValueError(f"{what}: one uint64 per rule")
+        return a if R else np.zeros(1, dtype=np.uint64)
+
+    mc = MESSAGE_CODES if msg_codes is None else int(msg_codes)
+    if not 0 <= mc <= 0xFF:
+        raise ValueError("msg_codes: one byte of SEL(v) bits")
+    return one(salts, "salts"), one(msg_salts, "msg_salts"), mc
+
+
+def rule_salts(ps: PolicySet) -> np.ndarray:
+    """The default fingerprint salts of ps's rules (kpe_fp_rule_salts): mix64 of the FNV-1a-64 hash
+    of each "<policy>/<rule>" name, never 0. (R,) uint64; XOR a policy's resourceVersion or an edit
+    counter into its rules' entries to make the msg_salts of row_fingerprints."""
+    out = np.zeros(ps.num_rules, dtype=np.uint64)
+    check(load().kpe_fp_rule_salts(ps.h, out.ctypes.data if out.size else None))
+    return out
+
+
+def row_fingerprints(verdicts, salts, msg_salts=None, msg_codes=None, cv_masks=None) -> np.ndarray:
+    """The fingerprint of each row of an (n, R) verdict matrix the caller holds
+    (kpe_row_fingerprints_host; no device call): (n,) uint64, 0 for a row without responses. salts:
+    one per rule; msg_salts / msg_codes as Engine.row_fingerprints; cv_masks: the (n, R) words of
+    Engine.cv_masks(raw=True), whose FAIL cells then count (KPE_FP_MASKS)."""
+    v = np.ascontiguousarray(verdicts, dtype=np.uint8)
+    if v.ndim == 1:
+        v = v.reshape(1, -1)
+    if v.ndim != 2:
+        raise ValueError("verdicts: rows of one cell per rule")
+    n, R = v.shape
+    s, ms, mc = _fp_salts(R, salts, msg_salts, msg_codes)
+    if s is None:
+        raise ValueError("salts: one uint64 per rule (rule_salts(ps))")
+    m = None
+    if cv_masks is not None:
+        m = np.ascontiguousarray(cv_masks, dtype=np.uint32).reshape(v.shape)
+    out = np.zeros(n, dtype=np.uint64)
+    check(load().kpe_row_fingerprints_host(R, v.ctypes.data if v.size else None, _ptr(m) if v.size else None, n, _ptr(s),
+                                           _ptr(ms), mc, FP_MASKS if m is not None else 0,
+                                           out.ctypes.data if n else None))
+    return out
+
+
+def changed_fingerprints(old, new, cap: Optional[int] = None) -> np.ndarray:
+    """The rows whose fingerprints differ (kpe_changed_fingerprints_host): uint64, ascending; at most
+    cap of them."""
+    a, b = np.ascontiguousarray(old, dtype=np.uint64), np.ascontiguousarray(new, dtype=np.uint64)
+    if a.ndim != 1 or a.shape != b.shape:
+        raise ValueError("old, new: one fingerprint per row, the same rows")
+    k = a.size if cap is None else min(int(cap), a.size)
+    rows = np.zeros(k, dtype=np.uint64)
+    t = load().kpe_changed_fingerprints_host(a.ctypes.data if a.size else None, b.ctypes.data if b.size else None, a.size,
+                                             rows.ctypes.data if k else None, k)
+    if t < 0:
+        check(-t)
+    return rows[:min(int(t), k)]
 
 
 def cli_summary(ps: PolicySet, counts: List[dict], audit_warn: bool = False) -> Dict[str, int]:

@@ -15,7 +15,7 @@ import json
 import numpy as np
 
 from ._lib import KpeError, load
-from .engine import SEL, Corpus
+from .engine import SEL, Corpus, rule_salts
 
 
 def resource_hash(resource) -> str:
@@ -124,17 +124,53 @@ class ResidentScanner:
     The background controller re-evaluates every resource after a policy or PolicyException change
     and writes a report only when it differs from the stored one (pkg/controllers/report/
     background/controller.go:379-419,463; ReportsAreIdentical, pkg/controllers/report/utils/
-    utils.go:66-88). Here the last result stays on the device (Engine.keep_results) and the
-    comparison runs there (Engine.changed_rows): the unchanged rows never cross to the host."""
+    utils.go:66-88). Here the last result stays on the device (Engine.keep_results, or with
+    keep="fingerprints" Engine.keep_fingerprints) and the comparison runs there (Engine.changed_rows,
+    Engine.changed_rows_fp): the unchanged rows never cross to the host."""
 
     MESSAGE_CODES = SEL(2) | SEL(4) | SEL(5)  # FAIL, ERROR, SKIP: results whose message the policy text decides
 
-    def __init__(self, engine, ndjson: bytes, ns_labels=None):
+    def __init__(self, engine, ndjson: bytes, ns_labels=None, keep="matrix", fingerprints=None, edits=None):
+        """keep="matrix" (the default): the last verdict matrix stays on the device (N x R bytes) and
+        the comparison is exact. keep="fingerprints": 8 bytes per row stay (Engine.keep_fingerprints;
+        two different result sets of a row collide with probability 2^-64), they do not depend on
+        the rule order, and they can be saved (`fingerprints()`, `edits`) and given back
+        (`fingerprints=`, `edits=`) to a scanner over a re-uploaded corpus or in a new process: its
+        first `apply` then returns only the rows that really changed."""
+        if keep not in ("matrix", "fingerprints"):
+            raise ValueError('keep: "matrix" or "fingerprints"')
+        if keep != "fingerprints" and (fingerprints is not None or edits is not None):
+            raise ValueError('fingerprints, edits: only with keep="fingerprints"')
         self.engine = engine
+        self.keep = keep
         nsl = json.dumps(ns_labels).encode() if isinstance(ns_labels, dict) else ns_labels
         self.corpus = Corpus(ndjson, nsl).upload(engine.device)
         self._policies = None  # the PolicySet of the kept result (held while its matrix is kept)
+        self.edits = dict(edits or {})  # policy name -> edits seen (keep="fingerprints": folded into msg_salts)
+        if fingerprints is not None:
+            engine.load_fingerprints(self.corpus, fingerprints)
         self.last_stats = {}
+
+    def fingerprints(self):
+        """keep="fingerprints": the kept fingerprints, one uint64 per row (None before the first
+        apply): what a caller stores with the reports, together with `edits`."""
+        return self.engine.kept_fingerprints(self.corpus) if self.keep == "fingerprints" else None
+
+    def _apply_fp(self, policies, edited):
+        eng, corpus = self.engine, self.corpus
+        for name in set(edited):
+            self.edits[name] = self.edits.get(name, 0) + 1
+        msg = rule_salts(policies)
+        for r, n in enumerate(policies.rule_names):
+            msg[r] ^= np.uint64(self.edits.get(n.split("/", 1)[0], 0))
+        eng.evaluate_async(policies, corpus)
+        if eng.kept_fingerprints(corpus, 0, 0) is None:
+            # nothing to compare with: against "no report" (fingerprint 0), every row that has a response
+            eng.load_fingerprints(corpus, np.zeros(corpus.n, dtype=np.uint64))
+        rows, vr, _, total = eng.changed_rows_fp(policies, corpus, msg_salts=msg, msg_codes=self.MESSAGE_CODES)
+        eng.keep_fingerprints(policies, corpus, msg_salts=msg, msg_codes=self.MESSAGE_CODES)
+        self.last_stats = {"rows": corpus.n, "changed": total}
+        return {int(i): vr[k].copy() for k, i in enumerate(rows)}
 
     def apply(self, policies, edited=()):
         """Evaluate `policies` (a PolicySet) on the corpus and return {row: verdict row} of the rows
@@ -142,6 +178,8 @@ class ResidentScanner:
         Rules are paired by "<policy>/<rule>" name. `edited` names policies whose text changed
         under the same name: their FAIL / ERROR / SKIP cells count as changed whatever they were,
         since the message may differ under an equal verdict."""
+        if self.keep == "fingerprints":
+            return self._apply_fp(policies, edited)
         eng, corpus = self.engine, self.corpus
         eng.evaluate_async(policies, corpus)
         if self._policies is None:
