@@ -619,6 +619,76 @@ typedef struct kpe_report_args {
 } kpe_report_args;
 long kpe_report_results_ex(const kpe_report_args* args, char* buf, size_t cap);
 
+/* ---- reports for a row list -------------------------------------------------- */
+/* The last step of the delta pipeline (kpe_changed_rows / kpe_changed_rows_fp give the rows whose
+ * report changes): for a list of rows the device selects the cells whose report entry needs detail
+ * and gathers it, one call brings it back in sparse form, and one host call renders every listed
+ * report. The per-row calls above are the specification: the bulk path reproduces them byte for byte.
+ *
+ * Which cells need which detail, per rule, in the KPE_SEL convention of kpe_select_cells (R bytes
+ * each): cell (row, r) with verdict v needs the kind iff (sel[r] >> v) & 1.
+ *   mask_sel    : the check mask word: a KPE_FAIL cell of a podSecurity rule; 0 for other rules;
+ *   cond_sel    : the condition trace words: a KPE_FAIL / KPE_ERROR / KPE_SKIP cell of a rule with a
+ *                 condition trace slot; 0 for a rule without one;
+ *   pattern_sel : the pattern record: a KPE_FAIL cell of a validate.pattern / anyPattern rule, a
+ *                 KPE_PASS cell of an anyPattern rule, a KPE_FAIL / KPE_ERROR cell of a validate.foreach
+ *                 rule with a pattern entry; 0 for a rule without a pattern walk.
+ * KPE_NA and KPE_UNDECIDED are never selected. Host only. */
+kpe_status kpe_report_detail_need(const kpe_program* prog, uint8_t* mask_sel, uint8_t* cond_sel, uint8_t* pattern_sel);
+
+#define KPE_RR_MASKS 1u
+#define KPE_RR_COND 2u
+#define KPE_RR_PATTERNS 4u
+/* Three sparse lists over the listed rows. A cell is named k * R + r, k the position in rows[] (not
+ * the row id), so the lists are self-contained for the renderer. Each list is ascending in that
+ * index and holds the first min(total, cap) entries; nothing past that is written. A cap of 0 with
+ * null pointers counts only. The totals are always written.
+ *   mask_words     : per cell exactly the word kpe_fetch_cv_masks returns for it (KPE_CVM_XMATCH
+ *                    included);
+ *   cond_words     : per cell exactly the KPE_CTRACE_WORDS words kpe_fetch_cond_traces_ex returns
+ *                    for it (words the rule's slot does not have are zero);
+ *   pattern_traces : per cell exactly the record kpe_pattern_traces returns for the absolute cell
+ *                    rows[k] * R + r, the element walk of a foreach cell included;
+ *   verdict_rows   : when not NULL, the nrows x R verdict cells of the listed rows. */
+typedef struct kpe_report_rows {
+  uint8_t* verdict_rows;                               /* nrows x R, or NULL */
+  uint64_t* mask_cells;    uint32_t* mask_words;       uint64_t mask_cap;    /* 1 word per cell */
+  uint64_t* cond_cells;    uint32_t* cond_words;       uint64_t cond_cap;    /* KPE_CTRACE_WORDS per cell */
+  uint64_t* pattern_cells; uint32_t* pattern_traces;   uint64_t pattern_cap; /* KPE_TRACE_ROOTS*KPE_TRACE_WORDS per cell */
+  uint64_t mask_total, cond_total, pattern_total;      /* out */
+} kpe_report_rows;
+/* After an evaluation of prog on the corpus, under the state rules of kpe_fetch_row_summaries (waits
+ * for it). rows[]: any order, duplicates allowed, every entry < N. flags: the kinds to gather; a kind
+ * whose flag is not set gives total 0 and its arrays are not read. KPE_E_INVALID for a null argument,
+ * an unknown flag, a cap without its arrays or a row past N, all checked before any device call;
+ * KPE_E_STATE without an evaluation of prog, or for KPE_RR_MASKS after an evaluation without masks (as
+ * kpe_fetch_cv_masks). No rule limit. The scratch belongs to the device handle and is kept between
+ * calls. */
+kpe_status kpe_fetch_report_rows(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint64_t* rows,
+                                 uint64_t nrows, uint32_t flags, kpe_report_rows* io);
+/* The specification twin of the selection, a plain double loop over dense inputs the caller holds for
+ * the listed rows: nrows x R verdicts, nrows x R mask words (may be NULL without KPE_RR_MASKS) and
+ * nrows x R x KPE_CTRACE_WORDS trace words (may be NULL without KPE_RR_COND). Same lists, caps and
+ * totals; of the pattern kind only pattern_cells is written (there are no records without a device)
+ * and verdict_rows is not touched. Host only. */
+kpe_status kpe_report_cells_host(const kpe_program* prog, uint64_t nrows, const uint8_t* verdict_rows,
+                                 const uint32_t* cv_mask_rows, const uint32_t* cond_ex_rows, uint32_t flags,
+                                 kpe_report_rows* io);
+/* The bulk renderer: `in` carries verdict_rows, the three lists and their entry counts in the *_total
+ * fields (fewer entries than the device total is legal when a list was truncated; null lists are
+ * legal). Row k's JSON array is buf[offsets[k] .. offsets[k+1]), with no separators; offsets has
+ * nrows + 1 entries and is always written. resources[k] (resource_lens[k] bytes) may be NULL: then
+ * row k gets no messages, as kpe_report_results gives. Returns the total length; when it is >= cap
+ * nothing useful is in buf and the caller calls again, as with kpe_report_results; a negative return
+ * is -kpe_status. For every row the bytes equal kpe_report_results_ex over the row's dense inputs,
+ * where an input is NULL when the row has no entry in that list (so the rows past the cut of a
+ * truncated list render without that detail). Rows are rendered on up to 16 threads
+ * (KPE_REPORT_THREADS lowers it); the output does not depend on the thread count. Host only; no
+ * device call. */
+long kpe_report_results_rows(const kpe_program* prog, const kpe_corpus* corpus, uint64_t nrows,
+                             const kpe_report_rows* in, const char* const* resources, const size_t* resource_lens,
+                             char* buf, size_t cap, uint64_t* offsets /* nrows + 1 */);
+
 /* ---- instrumentation (HIP events on the evaluation stream) ---------------- */
 typedef struct kpe_kernel_stats {
   uint64_t launches;        /* timed launches since the last reset: one per evaluation, one per

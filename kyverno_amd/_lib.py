@@ -163,6 +163,14 @@ def load():
     L.kpe_report_results_ex.argtypes = [vp, ctypes.c_char_p, sz]
     L.kpe_fetch_cond_traces_ex.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp]
     L.kpe_report_results_ex.restype = ctypes.c_long
+    L.kpe_report_detail_need.argtypes = [vp, vp, vp, vp]
+    L.kpe_report_detail_need.restype = ctypes.c_int
+    L.kpe_fetch_report_rows.argtypes = [vp, vp, vp, vp, u64, u32, vp]
+    L.kpe_fetch_report_rows.restype = ctypes.c_int
+    L.kpe_report_cells_host.argtypes = [vp, u64, vp, vp, vp, u32, vp]
+    L.kpe_report_cells_host.restype = ctypes.c_int
+    L.kpe_report_results_rows.argtypes = [vp, vp, u64, vp, vp, vp, vp, sz, vp]
+    L.kpe_report_results_rows.restype = ctypes.c_long
     L.kpe_cli_summary.argtypes = [vp, ctypes.POINTER(Counts), i32, ctypes.POINTER(CliTotals)]
     L.kpe_device_set_timing.argtypes = [vp, i32]
     L.kpe_device_kernel_stats.argtypes = [vp, vp, vp, ctypes.POINTER(KernelStats), i32]

@@ -43,6 +43,35 @@ struct KpeNsItem {
   uint32_t g, begin, end, single;
 };
 
+// Report detail of a row list (kpe_launch_report_need_scatter, report_rows.inl). Src: rows[] (every
+// entry a row of the corpus), the N x R check mask words (read only for mask hits), the N x nmsg
+// condition trace words and the per-rule slot table (KPE_RR_SLOT; both read only for cond hits).
+// Out: per kind the list of compact cells and its payload, written below the kind's cap only;
+// pattern_abs holds the absolute cell rows[i] * R + r, the list kpe_launch_pattern_trace takes.
+// slot table entry of a rule: its first word in a row's nmsg condition trace words << 3 | how many
+// words it has (0: no slot, 1, or KPE_FE_TRACE_WORDS for a validate.foreach rule)
+#define KPE_RR_SLOT(first, width) (((uint32_t)(first) << 3) | (uint32_t)(width))
+#define KPE_RR_SLOT_FIRST(e) ((e) >> 3)
+#define KPE_RR_SLOT_WIDTH(e) ((e) & 7u)
+struct KpeRrSrc {
+  const uint64_t* rows;
+  const uint32_t* masks;
+  const uint32_t* mtrace;
+  const uint32_t* slot;
+  uint32_t nmsg, pad_;
+};
+struct KpeRrOut {
+  uint64_t* mask_cells;
+  uint32_t* mask_words;  // 1 per cell
+  uint64_t mask_cap;
+  uint64_t* cond_cells;
+  uint32_t* cond_words;  // 4 per cell
+  uint64_t cond_cap;
+  uint64_t* pattern_cells;
+  uint64_t* pattern_abs;
+  uint64_t pattern_cap;
+};
+
 struct PredJob {
   uint32_t domain;
   uint32_t pat0, npat;  // patterns [pat0, pat0+npat) of the pattern table

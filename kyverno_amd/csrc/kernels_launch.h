@@ -83,4 +83,20 @@ hipError_t kpe_launch_row_fp(const uint8_t* v, const uint32_t* masks, uint32_t R
 hipError_t kpe_launch_fp_diff(const uint64_t* a, const uint64_t* b, uint64_t n, uint8_t* flags, hipStream_t s);
 // out[i] = fp[rows[i]], m words
 hipError_t kpe_launch_fp_gather(const uint64_t* fp, const uint64_t* rows, uint64_t m, uint64_t* out, hipStream_t s);
+
+// report detail of a row list (kpe_fetch_report_rows) over the compact matrix v of `cells` cells
+// (a multiple of R). need: 3 R bytes, [mask][cond][pattern] in the KPE_SEL convention, bit 0
+// (KPE_NA) clear in every byte. tile_counts: 3 * ntiles words (+ padding to a multiple of four),
+// tile_offs: 3 * ntiles + 1 offsets, ntiles = kpe_report_need_tiles(cells); kind k's hits are
+// tile_offs[(k + 1) * ntiles] - tile_offs[k * ntiles]. The count launcher also runs the scan.
+uint64_t kpe_report_need_tiles(uint64_t cells);
+hipError_t kpe_launch_report_need_count(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* need,
+                                        uint32_t* tile_counts, uint64_t* tile_offs, hipStream_t s);
+hipError_t kpe_launch_report_need_scatter(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* need,
+                                          const uint64_t* tile_offs, const KpeRrSrc* src, const KpeRrOut* out,
+                                          hipStream_t s);
+// out[i * KPE_FE_TRACE_WORDS + w]: the condition trace words of cell cells[i] (row * R + column) when
+// its rule is a validate.foreach rule with a slot, zeros otherwise (slot: KPE_RR_SLOT per rule)
+hipError_t kpe_launch_fe_words_gather(const uint64_t* cells, uint64_t n, uint32_t R, const uint32_t* slot,
+                                      const uint32_t* mtrace, uint32_t nmsg, uint32_t* out, hipStream_t s);
 }

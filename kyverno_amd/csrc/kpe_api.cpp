@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +16,7 @@
 #include <new>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/kpe.h"
@@ -147,6 +149,10 @@ struct kpe_device {
   // bytes per row of the largest corpus compared so far, kept between calls (an allocation of
   // that size costs more than the kernels). Used under mu by calls that wait before they return.
   DevBuf fp_scratch;
+  // kpe_fetch_report_rows' scratch, kept between calls for the same reason: the uploaded row list,
+  // the compact matrix, the tiles and the tables (rr_scratch), and the gathered lists with their
+  // payloads (rr_out), each as large as the largest call so far needed
+  DevBuf rr_scratch, rr_out;
   // kpe_fetch_namespace_counts with timing on: the last call's kernel time (HIP events) and the
   // last rows-by-namespace index build + upload (host clock)
   double ns_kernel_ms = 0, ns_index_ms = 0;
@@ -1317,7 +1323,14 @@ kpe_status ensure_binding(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc
     }
     HIPCHK(upload(B.cfkeys, fk, s));
     B.cargs_valid = false;
-    if (!P.pat.vars.empty()) HIPCHK(B.pvals.ensure((size_t)C.n * P.pat.vars.size() * 8 + 8));
+    if (!P.pat.vars.empty()) {
+      // zeroed (PVK_NULL) per binding: the condition kernel resolves a rule's variables only in the
+      // cells it evaluates, and kpe_pattern_traces may be asked for any cell of the matrix; the
+      // pattern VM indexes its tables by what a slot holds
+      const size_t bytes = (size_t)C.n * P.pat.vars.size() * 8 + 8;
+      HIPCHK(B.pvals.ensure(bytes));
+      HIPCHK(hipMemsetAsync(B.pvals.p, 0, bytes, s));
+    }
     if (P.cond.nmsg) {
       const size_t bytes = (size_t)C.n * P.cond.nmsg * 4;
       HIPCHK(B.mtrace.ensure(bytes + 4));
@@ -2988,6 +3001,34 @@ static int64_t fe_decider(const kpe::Program& P, const kpe::RuleReport& rr, uint
   return e;
 }
 
+// The condition trace slot of every rule (kernels_abi.h KPE_RR_SLOT): where its words start in a
+// row's nmsg words and how many it has (kpe_fetch_cond_traces_ex's expansion, per rule)
+static std::vector<uint32_t> cond_slot_table(const kpe::Program& P) {
+  std::vector<uint32_t> slot(P.rules.size(), 0u);
+  for (const KpeCRule& cr : P.cond.rules)
+    if (cr.mslot) slot[cr.col] = KPE_RR_SLOT(cr.mslot - 1u, cr.kind == CR_FOREACH ? KPE_FE_TRACE_WORDS : 1u);
+  return slot;
+}
+// The pattern trace jobs of listed cells (kpe_launch_pattern_trace): w holds KPE_FE_TRACE_WORDS
+// condition trace words per cell, cells[i] % R is the cell's rule. A FAIL / ERROR cell of a validate.foreach
+// rule that a pattern entry decided walks that entry's roots on the element it validated; every
+// other cell's job stays zero. jobs is left empty when no cell has one.
+static void fe_pat_jobs(const kpe::Program& P, const std::vector<uint32_t>& slot, const uint64_t* cells, const uint32_t* w,
+                        uint64_t ncells, std::vector<uint4>& jobs) {
+  const size_t R = P.rules.size();
+  for (uint64_t i = 0; i < ncells; ++i, w += KPE_FE_TRACE_WORDS) {
+    const uint32_t c = (uint32_t)(cells[i] % R);
+    if (KPE_RR_SLOT_WIDTH(slot[c]) != KPE_FE_TRACE_WORDS) continue;
+    if (jobs.empty()) jobs.assign(ncells, make_uint4(0u, 0u, 0u, 0u));
+    if (FT_KIND(w[1]) != FT_PAT || w[3] == 0xFFFFFFFEu) continue;
+    const int64_t e = fe_decider(P, P.reports[c], w[1]);
+    if (e < 0) continue;
+    const KpeCForeach& fe = P.cond.fes[(size_t)e];
+    if (fe.kind != FE_PAT) continue;
+    jobs[i] = make_uint4(fe.a, fe.b, w[3], 1u);
+  }
+}
+
 kpe_status kpe_pattern_traces(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint64_t* cells,
                               uint64_t ncells, uint32_t* out) {
   if (!dev || !prog || !c || !c->d || (ncells && (!cells || !out))) return fail(KPE_E_INVALID, "null argument");
@@ -3005,28 +3046,22 @@ kpe_status kpe_pattern_traces(kpe_device* dev, const kpe_program* prog, const kp
   const size_t rec = (size_t)KPE_TRACE_ROOTS * KPE_TRACE_WORDS;
   hipStream_t s = B.last ? B.last : dev->stream;
   // foreach cells decided by a pattern entry: the entry's roots on the element (the condition
-  // kernel's trace words of the cell)
+  // kernel's trace words of the cells: one gather, one copy)
   std::vector<uint4> jobs;
   if (P.any_fe_pat && B.cargs_valid && P.cond.nmsg) {
-    std::vector<int32_t> slot(R, -1);
-    for (const KpeCRule& cr : P.cond.rules)
-      if (cr.mslot && cr.kind == CR_FOREACH) slot[cr.col] = (int32_t)cr.mslot - 1;
+    const std::vector<uint32_t> slot = cond_slot_table(P);
+    DevBuf dcl, dsl, dw;
+    std::vector<uint32_t> w(ncells * KPE_FE_TRACE_WORDS);
+    HIPCHK(dcl.ensure(ncells * 8));
+    HIPCHK(dsl.ensure(R * 4));
+    HIPCHK(dw.ensure(w.size() * 4));
+    HIPCHK(hipMemcpyAsync(dcl.p, cells, ncells * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dsl.p, slot.data(), R * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(kpe_launch_fe_words_gather(dcl.as<uint64_t>(), ncells, (uint32_t)R, dsl.as<uint32_t>(),
+                                      B.mtrace.as<uint32_t>(), P.cond.nmsg, dw.as<uint32_t>(), s));
+    HIPCHK(hipMemcpyAsync(w.data(), dw.p, w.size() * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    for (uint64_t i = 0; i < ncells; ++i) {
-      const uint64_t row = cells[i] / R;
-      const uint32_t col = (uint32_t)(cells[i] % R);
-      if (slot[col] < 0) continue;
-      if (jobs.empty()) jobs.assign(ncells, make_uint4(0u, 0u, 0u, 0u));
-      uint32_t w[KPE_FE_TRACE_WORDS];
-      HIPCHK(hipMemcpy(w, B.mtrace.as<uint32_t>() + row * P.cond.nmsg + (size_t)slot[col], sizeof w,
-                       hipMemcpyDeviceToHost));
-      if (FT_KIND(w[1]) != FT_PAT || w[3] == 0xFFFFFFFEu) continue;
-      const int64_t e = fe_decider(P, P.reports[col], w[1]);
-      if (e < 0) continue;
-      const KpeCForeach& fe = P.cond.fes[(size_t)e];
-      if (fe.kind != FE_PAT) continue;
-      jobs[i] = make_uint4(fe.a, fe.b, w[3], 1u);
-    }
+    fe_pat_jobs(P, slot, cells, w.data(), ncells, jobs);
   }
   if (P.pat.rules.empty() && jobs.empty()) {  // no pattern walk: every record is empty
     memset(out, 0, ncells * rec * 4);
@@ -3503,6 +3538,11 @@ long kpe_report_results_msg_tr(const kpe_program* prog, const kpe_corpus* corpus
   return report_impl(prog, corpus, verdict_row, cv_mask_row, traces, nullptr, resource_json, resource_len, buf, cap);
 }
 
+// the row's JSON array into o (prog and verdict_row are not null)
+static void report_render(const kpe_program* prog, const kpe_corpus* corp, const uint8_t* verdict_row,
+                          const uint32_t* cv_mask_row, const uint32_t* traces, const uint32_t* cond_traces,
+                          const char* resource_json, size_t resource_len, const uint32_t* cond_traces_ex, std::string& o);
+
 static long report_impl(const kpe_program* prog, const kpe_corpus* corp, const uint8_t* verdict_row,
                         const uint32_t* cv_mask_row, const uint32_t* traces, const uint32_t* cond_traces,
                         const char* resource_json, size_t resource_len, char* buf, size_t cap,
@@ -3511,13 +3551,26 @@ static long report_impl(const kpe_program* prog, const kpe_corpus* corp, const u
     fail(KPE_E_INVALID, "null argument");
     return -KPE_E_INVALID;
   }
+  std::string o;
+  report_render(prog, corp, verdict_row, cv_mask_row, traces, cond_traces, resource_json, resource_len, cond_traces_ex, o);
+  if (buf && cap > 0) {
+    const size_t n = std::min(o.size(), cap - 1);
+    memcpy(buf, o.data(), n);
+    buf[n] = 0;
+  }
+  return (long)o.size();
+}
+
+static void report_render(const kpe_program* prog, const kpe_corpus* corp, const uint8_t* verdict_row,
+                          const uint32_t* cv_mask_row, const uint32_t* traces, const uint32_t* cond_traces,
+                          const char* resource_json, size_t resource_len, const uint32_t* cond_traces_ex, std::string& o) {
   // the typed pod view for podSecurity fail messages, decoded on first use
   int pod_state = 0;  // 0 not decoded, 1 ok, -1 getSpec fails
   kpe::PodView pod;
   std::string kind;
   static const char* const kResult[6] = {nullptr, "pass", "fail", "warn", "error", "skip"};
   const kpe::Program& P = *prog->p;
-  std::string o = "[";
+  o = "[";
   bool first = true;
   for (size_t r = 0; r < P.rules.size(); ++r) {
     const uint8_t v = verdict_row[r];
@@ -3635,12 +3688,296 @@ static long report_impl(const kpe_program* prog, const kpe_corpus* corp, const u
     o += '}';
   }
   o += ']';
-  if (buf && cap > 0) {
-    const size_t n = std::min(o.size(), cap - 1);
-    memcpy(buf, o.data(), n);
-    buf[n] = 0;
+}
+
+// ---- reports for a row list: which cells need detail, the sparse fetch, the bulk renderer ------
+static_assert(KPE_CTRACE_WORDS == 4u && KPE_FE_TRACE_WORDS == KPE_CTRACE_WORDS, "four condition words per cell");
+static_assert(sizeof(uint4) == KPE_FE_TRACE_WORDS * 4u, "a foreach cell's words are one uint4");
+
+// some entry of a validate.foreach rule (nested ones included) walks a pattern
+static bool fe_has_pattern(const kpe::Program& P, uint32_t first, uint32_t count, int depth = 0) {
+  for (uint32_t e = first; e - first < count && e < P.fe_reports.size(); ++e) {
+    const kpe::FeReport& f = P.fe_reports[e];
+    if (f.kind == FE_PAT) return true;
+    if (f.kind == FE_NEST && depth < 16 && fe_has_pattern(P, f.nested0, f.nnested, depth + 1)) return true;
   }
-  return (long)o.size();
+  return false;
+}
+
+// What report_render and the functions it calls read, per rule and verdict:
+//   the mask word   of a FAIL cell of a podSecurity rule (controls, fail messages);
+//   the trace words of a FAIL / ERROR / SKIP cell of a rule with a slot (deny messages and foreach
+//                   elements, RuleError texts, the skip's cause); PASS and WARN read none;
+//   the pattern record of a FAIL cell of a pattern rule, a PASS cell of an anyPattern rule, and a
+//                   FAIL / ERROR cell of a foreach rule with a pattern entry.
+kpe_status kpe_report_detail_need(const kpe_program* prog, uint8_t* mask_sel, uint8_t* cond_sel, uint8_t* pattern_sel) {
+  if (!prog) return fail(KPE_E_INVALID, "null argument");
+  const kpe::Program& P = *prog->p;
+  const size_t R = P.rules.size();
+  if (R && (!mask_sel || !cond_sel || !pattern_sel)) return fail(KPE_E_INVALID, "null argument");
+  for (size_t r = 0; r < R; ++r) {
+    const kpe::RuleReport& rr = P.reports[r];
+    mask_sel[r] = rr.pss ? KPE_SEL(KPE_FAIL) : 0u;
+    cond_sel[r] = rr.cond_slot ? KPE_SEL(KPE_FAIL) | KPE_SEL(KPE_ERROR) | KPE_SEL(KPE_SKIP) : 0u;
+    uint32_t p = 0;
+    if (rr.pat_rule) p |= KPE_SEL(KPE_FAIL) | (rr.any_pattern ? KPE_SEL(KPE_PASS) : 0u);
+    if (rr.foreach && fe_has_pattern(P, rr.fe0, rr.nfe)) p |= KPE_SEL(KPE_FAIL) | KPE_SEL(KPE_ERROR);
+    pattern_sel[r] = (uint8_t)p;
+  }
+  return KPE_OK;
+}
+
+// the argument checks the three calls share; records: the pattern kind needs pattern_traces
+static kpe_status report_rows_args(uint32_t flags, const kpe_report_rows* io, bool records) {
+  if (!io) return fail(KPE_E_INVALID, "null argument");
+  if (flags & ~(KPE_RR_MASKS | KPE_RR_COND | KPE_RR_PATTERNS)) return fail(KPE_E_INVALID, "unknown flag");
+  if (((flags & KPE_RR_MASKS) && io->mask_cap && (!io->mask_cells || !io->mask_words)) ||
+      ((flags & KPE_RR_COND) && io->cond_cap && (!io->cond_cells || !io->cond_words)) ||
+      ((flags & KPE_RR_PATTERNS) && io->pattern_cap && (!io->pattern_cells || (records && !io->pattern_traces))))
+    return fail(KPE_E_INVALID, "cap > 0 without its arrays");
+  return KPE_OK;
+}
+// the three need tables of a call, [mask][cond][pattern]: a kind whose flag is not set selects nothing
+static kpe_status report_need_tables(const kpe_program* prog, uint32_t flags, std::vector<uint8_t>& need) {
+  const size_t R = prog->p->rules.size();
+  need.assign(3 * R + 1, 0);
+  const kpe_status st = kpe_report_detail_need(prog, need.data(), need.data() + R, need.data() + 2 * R);
+  if (st) return st;
+  for (size_t k = 0; k < 3; ++k)
+    if (!(flags & (1u << k))) memset(need.data() + k * R, 0, R);
+  return KPE_OK;
+}
+
+kpe_status kpe_report_cells_host(const kpe_program* prog, uint64_t nrows, const uint8_t* verdict_rows,
+                                 const uint32_t* cv_mask_rows, const uint32_t* cond_ex_rows, uint32_t flags,
+                                 kpe_report_rows* io) {
+  if (!prog) return fail(KPE_E_INVALID, "null argument");
+  kpe_status st = report_rows_args(flags, io, false);
+  if (st) return st;
+  const size_t R = prog->p->rules.size();
+  const uint64_t cells = nrows * R;
+  if (cells && (!verdict_rows || ((flags & KPE_RR_MASKS) && !cv_mask_rows) || ((flags & KPE_RR_COND) && !cond_ex_rows)))
+    return fail(KPE_E_INVALID, "null argument");
+  std::vector<uint8_t> need;
+  if ((st = report_need_tables(prog, flags, need))) return st;
+  uint64_t nm = 0, nc = 0, np = 0;
+  for (uint64_t k = 0; k < nrows; ++k)
+    for (size_t r = 0; r < R; ++r) {
+      const uint64_t cell = k * R + r;
+      const uint32_t v = verdict_rows[cell];
+      if (v >= 8u) continue;
+      if ((need[r] >> v) & 1u) {
+        if (nm < io->mask_cap) io->mask_cells[nm] = cell, io->mask_words[nm] = cv_mask_rows[cell];
+        ++nm;
+      }
+      if ((need[R + r] >> v) & 1u) {
+        if (nc < io->cond_cap) {
+          io->cond_cells[nc] = cell;
+          memcpy(io->cond_words + nc * KPE_CTRACE_WORDS, cond_ex_rows + cell * KPE_CTRACE_WORDS, KPE_CTRACE_WORDS * 4);
+        }
+        ++nc;
+      }
+      if ((need[2 * R + r] >> v) & 1u) {
+        if (np < io->pattern_cap) io->pattern_cells[np] = cell;
+        ++np;
+      }
+    }
+  io->mask_total = nm, io->cond_total = nc, io->pattern_total = np;
+  return KPE_OK;
+}
+
+kpe_status kpe_fetch_report_rows(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint64_t* rows,
+                                 uint64_t nrows, uint32_t flags, kpe_report_rows* io) {
+  if (!dev || !prog || !c || (nrows && !rows)) return fail(KPE_E_INVALID, "null argument");
+  kpe_status st = report_rows_args(flags, io, true);
+  if (st) return st;
+  io->mask_total = io->cond_total = io->pattern_total = 0;
+  const kpe::Program& P = *prog->p;
+  const size_t R = P.rules.size();
+  const uint64_t N = (uint64_t)c->c->n;
+  for (uint64_t k = 0; k < nrows; ++k)
+    if (rows[k] >= N) return fail(KPE_E_INVALID, "row past the corpus");
+  const uint64_t cells = nrows * R;
+  if (!cells) return KPE_OK;
+  if (!c->d) return fail(KPE_E_STATE, "corpus not uploaded");
+  std::vector<uint8_t> need;
+  if ((st = report_need_tables(prog, flags, need))) return st;
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  auto& B = c->d->bind;
+  if (B.prog != prog->p.get()) return fail(KPE_E_STATE, "no evaluation of this program on this corpus");
+  if (c->d->ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  if ((flags & KPE_RR_MASKS) && !c->d->has_masks) return fail(KPE_E_STATE, "check masks were not computed");
+  const uint32_t nmsg = P.cond.nmsg;
+  if ((flags & KPE_RR_COND) && nmsg && !B.cargs_valid)
+    return fail(KPE_E_STATE, "no evaluation of this program on this corpus");
+  const std::vector<uint32_t> slot = cond_slot_table(P);
+  for (size_t r = 0; r < R; ++r)  // a slot lies inside the row's words, or the rule has none
+    if (KPE_RR_SLOT_WIDTH(slot[r]) && KPE_RR_SLOT_FIRST(slot[r]) + KPE_RR_SLOT_WIDTH(slot[r]) > nmsg)
+      return fail(KPE_E_INVALID, "condition trace slot past the row's words");
+    else if (!KPE_RR_SLOT_WIDTH(slot[r])) need[R + r] = 0;
+  hipStream_t s = B.last ? B.last : dev->stream;
+
+  // stage 1 (rr_scratch): the row list, the compact matrix, the tiles, the tables
+  auto a16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
+  const uint64_t ntiles = kpe_report_need_tiles(cells);
+  const size_t o_rows = 0, o_v = o_rows + a16(nrows * 8), o_cnt = o_v + a16(cells);
+  const size_t o_off = o_cnt + a16((3 * ntiles + 3) / 4 * 16), o_need = o_off + a16((3 * ntiles + 1) * 8);
+  const size_t o_slot = o_need + a16(3 * R), s1_bytes = o_slot + a16(4 * R);
+  HIPCHK(dev->rr_scratch.ensure(s1_bytes));
+  uint8_t* s1 = dev->rr_scratch.as<uint8_t>();
+  uint64_t* d_rows = reinterpret_cast<uint64_t*>(s1 + o_rows);
+  uint8_t* d_v = s1 + o_v;
+  uint32_t* d_cnt = reinterpret_cast<uint32_t*>(s1 + o_cnt);
+  uint64_t* d_off = reinterpret_cast<uint64_t*>(s1 + o_off);
+  uint8_t* d_need = s1 + o_need;
+  uint32_t* d_slot = reinterpret_cast<uint32_t*>(s1 + o_slot);
+  HIPCHK(hipMemcpyAsync(d_rows, rows, nrows * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_need, need.data(), 3 * R, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_slot, slot.data(), 4 * R, hipMemcpyHostToDevice, s));
+  HIPCHK(kpe_launch_gather_rows(B.verdicts.as<uint8_t>(), (uint32_t)R, d_rows, nrows, d_v, s));
+  HIPCHK(kpe_launch_report_need_count(d_v, cells, (uint32_t)R, d_need, d_cnt, d_off, s));
+  uint64_t ends[4] = {0, 0, 0, 0};  // offs[0], offs[ntiles], offs[2 ntiles], offs[3 ntiles]: one strided copy
+  HIPCHK(hipMemcpy2DAsync(ends, 8, d_off, (size_t)ntiles * 8, 8, 4, hipMemcpyDeviceToHost, s));
+  if (io->verdict_rows) HIPCHK(hipMemcpyAsync(io->verdict_rows, d_v, cells, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  io->mask_total = ends[1] - ends[0], io->cond_total = ends[2] - ends[1], io->pattern_total = ends[3] - ends[2];
+  const uint64_t mm = (flags & KPE_RR_MASKS) ? std::min(io->mask_total, io->mask_cap) : 0;
+  const uint64_t mc = (flags & KPE_RR_COND) ? std::min(io->cond_total, io->cond_cap) : 0;
+  const uint64_t mp = (flags & KPE_RR_PATTERNS) ? std::min(io->pattern_total, io->pattern_cap) : 0;
+  if (!(mm | mc | mp)) return KPE_OK;
+
+  // stage 2 (rr_out): the lists and their payloads, sized by what is written
+  const size_t rec = (size_t)KPE_TRACE_ROOTS * KPE_TRACE_WORDS * 4;
+  const size_t o_mcell = 0, o_ccell = o_mcell + a16(mm * 8), o_pcell = o_ccell + a16(mc * 8);
+  const size_t o_pabs = o_pcell + a16(mp * 8);
+  const size_t o_cw = o_pabs + a16(mp * 8), o_job = o_cw + a16(mc * 16), o_few = o_job + a16(mp * 16);
+  const size_t o_rec = o_few + a16(mp * 16), o_mw = o_rec + a16(mp * rec), s2_bytes = o_mw + a16(mm * 4);
+  HIPCHK(dev->rr_out.ensure(s2_bytes));
+  uint8_t* s2 = dev->rr_out.as<uint8_t>();
+  KpeRrSrc src{d_rows, B.masks.as<uint32_t>(), B.mtrace.as<uint32_t>(), d_slot, nmsg, 0u};
+  KpeRrOut out{reinterpret_cast<uint64_t*>(s2 + o_mcell), reinterpret_cast<uint32_t*>(s2 + o_mw), mm,
+               reinterpret_cast<uint64_t*>(s2 + o_ccell), reinterpret_cast<uint32_t*>(s2 + o_cw), mc,
+               reinterpret_cast<uint64_t*>(s2 + o_pcell), reinterpret_cast<uint64_t*>(s2 + o_pabs), mp};
+  HIPCHK(kpe_launch_report_need_scatter(d_v, cells, (uint32_t)R, d_need, d_off, &src, &out, s));
+  if (mm) {
+    HIPCHK(hipMemcpyAsync(io->mask_cells, out.mask_cells, mm * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->mask_words, out.mask_words, mm * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (mc) {
+    HIPCHK(hipMemcpyAsync(io->cond_cells, out.cond_cells, mc * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(io->cond_words, out.cond_words, mc * 16, hipMemcpyDeviceToHost, s));
+  }
+  if (mp) {
+    HIPCHK(hipMemcpyAsync(io->pattern_cells, out.pattern_cells, mp * 8, hipMemcpyDeviceToHost, s));
+    // foreach cells decided by a pattern entry: their jobs from their trace words, as kpe_pattern_traces
+    std::vector<uint4> jobs;
+    if (P.any_fe_pat && B.cargs_valid && nmsg) {
+      std::vector<uint32_t> w(mp * KPE_FE_TRACE_WORDS);
+      uint32_t* d_few = reinterpret_cast<uint32_t*>(s2 + o_few);
+      HIPCHK(kpe_launch_fe_words_gather(out.pattern_abs, mp, (uint32_t)R, d_slot, B.mtrace.as<uint32_t>(), nmsg, d_few, s));
+      HIPCHK(hipMemcpyAsync(w.data(), d_few, w.size() * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      fe_pat_jobs(P, slot, io->pattern_cells, w.data(), mp, jobs);
+    }
+    if (P.pat.rules.empty() && jobs.empty()) {  // no pattern walk: every record is empty
+      memset(io->pattern_traces, 0, mp * rec);
+    } else {
+      if (!B.pargs_valid) return fail(KPE_E_STATE, "the binding has no completed evaluation of its pattern rules");
+      uint4* d_job = reinterpret_cast<uint4*>(s2 + o_job);
+      uint32_t* d_rec = reinterpret_cast<uint32_t*>(s2 + o_rec);
+      if (!jobs.empty()) HIPCHK(hipMemcpyAsync(d_job, jobs.data(), mp * sizeof(uint4), hipMemcpyHostToDevice, s));
+      HIPCHK(kpe_launch_pattern_trace(B.pargs.as<PatArgs>(), out.pattern_abs, mp, d_rec, jobs.empty() ? nullptr : d_job,
+                                      s));
+      HIPCHK(hipMemcpyAsync(io->pattern_traces, d_rec, mp * rec, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));  // jobs is read by the upload until here
+    }
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return KPE_OK;
+}
+
+// threads of kpe_report_results_rows: up to 16, KPE_REPORT_THREADS lowers it
+static unsigned report_threads() {
+  unsigned n = 16;
+  if (const char* ev = getenv("KPE_REPORT_THREADS")) n = (unsigned)std::max(1, std::min(16, atoi(ev)));
+  return n;
+}
+
+long kpe_report_results_rows(const kpe_program* prog, const kpe_corpus* corpus, uint64_t nrows, const kpe_report_rows* in,
+                             const char* const* resources, const size_t* resource_lens, char* buf, size_t cap,
+                             uint64_t* offsets) {
+  if (!prog || !in || !offsets || (resources && !resource_lens)) {
+    fail(KPE_E_INVALID, "null argument");
+    return -KPE_E_INVALID;
+  }
+  const size_t R = prog->p->rules.size();
+  if (nrows && R && !in->verdict_rows) {
+    fail(KPE_E_INVALID, "null verdict_rows");
+    return -KPE_E_INVALID;
+  }
+  // a list is its cells and payload, `total` entries of them; a null list has none
+  const uint64_t nm = in->mask_cells && in->mask_words ? in->mask_total : 0;
+  const uint64_t nc = in->cond_cells && in->cond_words ? in->cond_total : 0;
+  const uint64_t np = in->pattern_cells && in->pattern_traces ? in->pattern_total : 0;
+  const size_t rec = (size_t)KPE_TRACE_ROOTS * KPE_TRACE_WORDS;
+  std::vector<std::string> outs(nrows);
+  const unsigned T = (unsigned)std::min<uint64_t>(std::max<uint64_t>(nrows, 1), report_threads());
+  std::atomic<uint64_t> next{0};
+  std::atomic<bool> bad{false};
+  // Rows in blocks of 64, handed out dynamically. A thread expands the row's entries of each list
+  // (ascending cells: the entries of row k are one run) into dense rows of its own, renders with the
+  // per-row renderer, and clears what it set. A row without an entry in a list renders without that
+  // input, as the per-row call with NULL for it does.
+  auto work = [&]() {
+    std::vector<uint32_t> mrow(nm ? R : 0, 0u), crow(nc ? R * KPE_CTRACE_WORDS : 0, 0u), prow(np ? R * rec : 0, 0u);
+    try {
+      for (uint64_t b; (b = next.fetch_add(64)) < nrows;)
+        for (uint64_t k = b; k < std::min(nrows, b + 64); ++k) {
+          const uint64_t c0 = k * R, c1 = c0 + R;
+          const uint64_t* m0 = std::lower_bound(in->mask_cells, in->mask_cells + nm, c0);
+          const uint64_t* q0 = std::lower_bound(in->cond_cells, in->cond_cells + nc, c0);
+          const uint64_t* p0 = std::lower_bound(in->pattern_cells, in->pattern_cells + np, c0);
+          const uint64_t *m1 = m0, *q1 = q0, *p1 = p0;
+          for (; m1 < in->mask_cells + nm && *m1 >= c0 && *m1 < c1; ++m1)
+            mrow[*m1 - c0] = in->mask_words[m1 - in->mask_cells];
+          for (; q1 < in->cond_cells + nc && *q1 >= c0 && *q1 < c1; ++q1)
+            memcpy(&crow[(*q1 - c0) * KPE_CTRACE_WORDS], in->cond_words + (q1 - in->cond_cells) * KPE_CTRACE_WORDS,
+                   KPE_CTRACE_WORDS * 4);
+          for (; p1 < in->pattern_cells + np && *p1 >= c0 && *p1 < c1; ++p1)
+            memcpy(&prow[(*p1 - c0) * rec], in->pattern_traces + (p1 - in->pattern_cells) * rec, rec * 4);
+          const char* res = resources ? resources[k] : nullptr;
+          report_render(prog, corpus, in->verdict_rows + c0, m1 != m0 ? mrow.data() : nullptr,
+                        p1 != p0 ? prow.data() : nullptr, nullptr, res, res ? resource_lens[k] : 0,
+                        q1 != q0 ? crow.data() : nullptr, outs[k]);
+          for (const uint64_t* x = m0; x < m1; ++x) mrow[*x - c0] = 0u;
+          for (const uint64_t* x = q0; x < q1; ++x) memset(&crow[(*x - c0) * KPE_CTRACE_WORDS], 0, KPE_CTRACE_WORDS * 4);
+          for (const uint64_t* x = p0; x < p1; ++x) memset(&prow[(*x - c0) * rec], 0, rec * 4);
+        }
+    } catch (...) {
+      bad = true;
+      next = nrows;
+    }
+  };
+  if (T <= 1) {
+    work();
+  } else {
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < T; ++t) th.emplace_back(work);
+    for (auto& x : th) x.join();
+  }
+  if (bad) {
+    fail(KPE_E_INVALID, "report rendering failed");
+    return -KPE_E_INVALID;
+  }
+  uint64_t total = 0;
+  for (uint64_t k = 0; k < nrows; ++k) offsets[k] = total, total += outs[k].size();
+  offsets[nrows] = total;
+  if (buf && total < cap) {
+    for (uint64_t k = 0; k < nrows; ++k) memcpy(buf + offsets[k], outs[k].data(), outs[k].size());
+    buf[total] = 0;
+  }
+  return (long)total;
 }
 
 kpe_status kpe_device_set_timing(kpe_device* dev, int enabled) {

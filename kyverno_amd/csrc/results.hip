@@ -7,6 +7,9 @@
 //  kpe_ns_count*_kernel  — per-namespace rule counts.
 //  kpe_delta_*_kernel, kpe_gather_rows_kernel — result deltas against a kept matrix.
 //  kpe_row_fp_kernel, kpe_fp_diff_kernel, kpe_fp_gather_kernel — row fingerprints and their compare.
+//  kpe_report_need_count_kernel, kpe_report_need_scatter_kernel, kpe_fe_words_gather_kernel — the
+//                          report detail of a row list (check mask words, condition trace words,
+//                          pattern cells).
 // None of them reads a program or runs a VM.
 #include "kernels_common.h"
 
@@ -672,6 +675,156 @@ extern "C" hipError_t kpe_launch_fp_gather(const uint64_t* fp, const uint64_t* r
   if (!m) return hipSuccess;
   const dim3 grid((unsigned)std::min<uint64_t>((m + 255u) / 256u, 1u << 16));
   hipLaunchKernelGGL(kpe_fp_gather_kernel, grid, dim3(256), 0, s, fp, rows, m, out);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Report detail of a row list (kpe_fetch_report_rows): the selection chain over the compact matrix
+// kpe_gather_rows_kernel made of the listed rows, for three need tables at once (report_rows.inl,
+// shared with scripts/report_rows_check.cpp). The count pass writes three counts per tile, kind k at
+// tile_counts[k * ntiles + tile]; kpe_select_scan_kernel scans the 3 * ntiles counts in one launch;
+// the scatter pass recomputes the hit masks and writes each hit's compact cell and its payload,
+// fetched through rows[]. Ordering is the selection's: tile offset + waves before (LDS) + lanes
+// before (DPP scan); no global cursor, no atomics. The need tables are staged in LDS up to
+// kSelLdsRules rules (48 KiB) and the slot table beside them up to kRrSlotLdsRules; past that they are
+// read from global memory: no rule limit.
+#define KPE_RR_FN __host__ __device__ __forceinline__
+#define KPE_RR_DEV __device__ __forceinline__
+namespace {
+__device__ __forceinline__ void rr_load16(const uint8_t* __restrict__ p, uint32_t cnt, uint32_t* w) {
+  const Cells16 c = load_cells(p, 0, cnt);
+  w[0] = c.w[0], w[1] = c.w[1], w[2] = c.w[2], w[3] = c.w[3];
+}
+#include "report_rows.inl"
+}  // namespace
+constexpr uint32_t kRrSlotLdsRules = 4096;  // the slot table's 4 R bytes staged beside the need tables
+static_assert(kRrTile == kSelTile, "the tiles of the selection kernels");
+
+template <bool LDS>
+__global__ void __launch_bounds__(256) kpe_report_need_count_kernel(const uint8_t* __restrict__ v, uint64_t cells, uint32_t R,
+                                                                    const uint8_t* __restrict__ need_g,
+                                                                    uint32_t* __restrict__ tile_counts, uint64_t ntiles) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_rr_dyn[];
+  __shared__ uint32_t s_w[2][kRrKinds][4];  // by tile parity: one barrier per tile
+  const uint32_t t = threadIdx.x;
+  const uint8_t* need = stage_table<LDS>(need_g, 3u * R, s_rr_dyn);
+  uint32_t par = 0;
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, par ^= 1u) {
+    uint32_t m[kRrKinds];
+    rr_lane_hits(v, cells, R, tile, t, need, m);
+#pragma unroll
+    for (uint32_t k = 0; k < kRrKinds; ++k) {
+      const uint32_t inc = wave_incl_scan((uint32_t)__popc(m[k]));
+      if ((t & 63u) == 63u) s_w[par][k][t >> 6] = inc;
+    }
+    __syncthreads();
+    if (t < kRrKinds) tile_counts[t * ntiles + tile] = s_w[par][t][0] + s_w[par][t][1] + s_w[par][t][2] + s_w[par][t][3];
+  }
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(256) kpe_report_need_scatter_kernel(const uint8_t* __restrict__ v, uint64_t cells,
+                                                                      uint32_t R, const uint8_t* __restrict__ need_g,
+                                                                      uint32_t slot_lds, const uint64_t* __restrict__ offs,
+                                                                      uint64_t ntiles, KpeRrSrc S, const KpeRrOut O) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_rr_dyn[];
+  __shared__ uint32_t s_w[kRrKinds][4];
+  const uint32_t t = threadIdx.x;
+  if (LDS && slot_lds) {  // uniform; behind the need tables, word aligned; stage_table's barrier covers it
+    uint32_t* l = reinterpret_cast<uint32_t*>(s_rr_dyn + ((3u * R + 3u) & ~3u));
+    for (uint32_t i = t; i < R; i += 256u) l[i] = S.slot[i];
+    S.slot = l;
+  }
+  const uint8_t* need = stage_table<LDS>(need_g, 3u * R, s_rr_dyn);
+  uint64_t base[kRrKinds];
+#pragma unroll
+  for (uint32_t k = 0; k < kRrKinds; ++k) base[k] = offs[k * ntiles];
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    uint64_t o0[kRrKinds], o1[kRrKinds];  // uniform
+#pragma unroll
+    for (uint32_t k = 0; k < kRrKinds; ++k) {
+      o0[k] = offs[k * ntiles + tile] - base[k];
+      o1[k] = offs[k * ntiles + tile + 1u] - base[k];
+    }
+    if (!rr_tile_live(o0, o1, O)) continue;
+    uint32_t m[kRrKinds], before[kRrKinds];
+    rr_lane_hits(v, cells, R, tile, t, need, m);
+#pragma unroll
+    for (uint32_t k = 0; k < kRrKinds; ++k) {
+      const uint32_t hits = (uint32_t)__popc(m[k]);
+      const uint32_t inc = wave_incl_scan(hits);
+      if ((t & 63u) == 63u) s_w[k][t >> 6] = inc;
+      before[k] = inc - hits;
+    }
+    __syncthreads();
+    uint64_t o[kRrKinds];
+#pragma unroll
+    for (uint32_t k = 0; k < kRrKinds; ++k) {
+#pragma unroll
+      for (uint32_t w = 0; w < 3u; ++w)
+        if (w < (t >> 6)) before[k] += s_w[k][w];
+      o[k] = o0[k] + before[k];
+    }
+    rr_lane_scatter(rr_lane_first(tile, t), m, o, R, S, O);
+    __syncthreads();
+  }
+}
+
+// One thread per listed cell: the four condition trace words of a validate.foreach cell, for the
+// pattern trace jobs of kpe_pattern_traces and kpe_fetch_report_rows (zeros for other rules).
+__global__ void __launch_bounds__(256) kpe_fe_words_gather_kernel(const uint64_t* __restrict__ cells, uint64_t n, uint32_t R,
+                                                                  const uint32_t* __restrict__ slot,
+                                                                  const uint32_t* __restrict__ mtrace, uint32_t nmsg,
+                                                                  uint4* __restrict__ out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
+    const uint64_t cell = cells[i];
+    const uint64_t row = rr_div(cell, R);
+    const uint32_t e = slot[(uint32_t)(cell - row * R)];
+    uint4 w = make_uint4(0u, 0u, 0u, 0u);
+    if (KPE_RR_SLOT_WIDTH(e) == KPE_FE_TRACE_WORDS) {
+      const uint32_t* src = mtrace + row * nmsg + KPE_RR_SLOT_FIRST(e);
+      w = make_uint4(src[0], src[1], src[2], src[3]);
+    }
+    out[i] = w;
+  }
+}
+
+extern "C" uint64_t kpe_report_need_tiles(uint64_t cells) { return (cells + kRrTile - 1u) / kRrTile; }
+extern "C" hipError_t kpe_launch_report_need_count(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* need,
+                                                   uint32_t* tile_counts, uint64_t* tile_offs, hipStream_t s) {
+  if (!cells || !R) return hipSuccess;
+  const uint64_t ntiles = kpe_report_need_tiles(cells);
+  const dim3 grid((unsigned)std::min<uint64_t>(ntiles, kSelGrid));
+  if (R <= kSelLdsRules)
+    hipLaunchKernelGGL(kpe_report_need_count_kernel<true>, grid, dim3(256), (size_t)3u * R, s, v, cells, R, need,
+                       tile_counts, ntiles);
+  else
+    hipLaunchKernelGGL(kpe_report_need_count_kernel<false>, grid, dim3(256), 0, s, v, cells, R, need, tile_counts, ntiles);
+  hipLaunchKernelGGL(kpe_select_scan_kernel, dim3(1), dim3(256), 0, s, tile_counts, tile_offs, kRrKinds * ntiles);
+  return hipGetLastError();
+}
+extern "C" hipError_t kpe_launch_report_need_scatter(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* need,
+                                                     const uint64_t* tile_offs, const KpeRrSrc* src, const KpeRrOut* out,
+                                                     hipStream_t s) {
+  if (!cells || !R || !(out->mask_cap | out->cond_cap | out->pattern_cap)) return hipSuccess;
+  const uint64_t ntiles = kpe_report_need_tiles(cells);
+  const dim3 grid((unsigned)std::min<uint64_t>(ntiles, kSelGrid));
+  const uint32_t slot_lds = R <= kRrSlotLdsRules ? 1u : 0u;
+  const size_t dyn = (((size_t)3u * R + 3u) & ~(size_t)3u) + (slot_lds ? (size_t)4u * R : 0u);
+  if (R <= kSelLdsRules)
+    hipLaunchKernelGGL(kpe_report_need_scatter_kernel<true>, grid, dim3(256), dyn, s, v, cells, R, need, slot_lds,
+                       tile_offs, ntiles, *src, *out);
+  else
+    hipLaunchKernelGGL(kpe_report_need_scatter_kernel<false>, grid, dim3(256), 0, s, v, cells, R, need, 0u, tile_offs,
+                       ntiles, *src, *out);
+  return hipGetLastError();
+}
+extern "C" hipError_t kpe_launch_fe_words_gather(const uint64_t* cells, uint64_t n, uint32_t R, const uint32_t* slot,
+                                                 const uint32_t* mtrace, uint32_t nmsg, uint32_t* out, hipStream_t s) {
+  if (!n) return hipSuccess;
+  const dim3 grid((unsigned)std::min<uint64_t>((n + 255u) / 256u, 1u << 16));
+  hipLaunchKernelGGL(kpe_fe_words_gather_kernel, grid, dim3(256), 0, s, cells, n, R, slot, mtrace, nmsg,
+                     reinterpret_cast<uint4*>(out));
   return hipGetLastError();
 }
 

@@ -592,6 +592,36 @@ class Engine:
             check(f(self.device.h, ps.h, corpus.h, row0, n, out.ctypes.data))
         return out
 
+    # ---- reports for a row list (the sparse detail of the listed rows, then one bulk render) ----
+    def fetch_report_rows(self, ps: PolicySet, corpus: Corpus, rows, masks=True, cond=True, patterns=True,
+                          caps=None) -> dict:
+        """What the reports of `rows` (row ids of corpus, any order, duplicates allowed) need beyond
+        their verdicts, gathered on the device after an evaluation of ps on corpus
+        (kpe_fetch_report_rows): a dict of verdict_rows (k, R) uint8 and three sparse lists over
+        compact cells (position in rows * R + column): mask_cells / mask_words (the raw cv mask
+        words, KPE_CVM_XMATCH included), cond_cells / cond_words (m, KPE_CTRACE_WORDS),
+        pattern_cells / pattern_traces (m, KPE_TRACE_ROOTS, KPE_TRACE_WORDS), and the device totals
+        mask_total, cond_total, pattern_total. masks needs an evaluation with masks. caps: at most
+        that many entries per list (mask, cond, pattern); None: a count call, then an exact one."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        rbuf = r if r.size else np.zeros(1, dtype=np.uint64)
+        flags = _rr_flags(masks, cond, patterns)
+
+        def call(io):
+            check(load().kpe_fetch_report_rows(self.device.h, ps.h, corpus.h, rbuf.ctypes.data, r.size, flags,
+                                               ctypes.byref(io)))
+
+        return _rr_two_calls(call, r.size, ps.num_rules, caps, records=True)
+
+    def report_rows(self, ps: PolicySet, corpus: Corpus, rows, resources=None, masks=True, cond=True,
+                    patterns=True) -> List[List[dict]]:
+        """The PolicyReport results of each listed row of the last evaluation of ps on corpus, as
+        report_results gives them with the row's traces, condition traces and raw mask words: one
+        fetch_report_rows (a count call and an exact call) and one render_report_rows. resources: a
+        list aligned with rows of dicts or JSON bytes (None entries, or None: no messages)."""
+        sp = self.fetch_report_rows(ps, corpus, rows, masks=masks, cond=cond, patterns=patterns)
+        return render_report_rows(ps, sp, resources=resources, corpus=corpus)
+
     # ---- reference-shaped API ----
     def validate_batch(self, policies: Sequence[dict], resources: Sequence[dict],
                        namespace_labels: Optional[Dict[str, Dict[str, str]]] = None) -> List[List[EngineResponse]]:
@@ -701,6 +731,129 @@ def report_results(ps: PolicySet, verdict_row, cv_mask_row=None, resource=None, 
         if n < cap:
             return json.loads(buf.value.decode())
         cap = n + 1
+
+
+RR_MASKS, RR_COND, RR_PATTERNS = 1, 2, 4  # include/kpe.h KPE_RR_*
+
+
+class ReportRows(ctypes.Structure):
+    """include/kpe.h kpe_report_rows"""
+    _fields_ = [("verdict_rows", ctypes.c_void_p),
+                ("mask_cells", ctypes.c_void_p), ("mask_words", ctypes.c_void_p), ("mask_cap", ctypes.c_uint64),
+                ("cond_cells", ctypes.c_void_p), ("cond_words", ctypes.c_void_p), ("cond_cap", ctypes.c_uint64),
+                ("pattern_cells", ctypes.c_void_p), ("pattern_traces", ctypes.c_void_p),
+                ("pattern_cap", ctypes.c_uint64),
+                ("mask_total", ctypes.c_uint64), ("cond_total", ctypes.c_uint64), ("pattern_total", ctypes.c_uint64)]
+
+
+def _rr_flags(masks, cond, patterns) -> int:
+    return (RR_MASKS if masks else 0) | (RR_COND if cond else 0) | (RR_PATTERNS if patterns else 0)
+
+
+def _rr_two_calls(call, nrows: int, R: int, caps, records: bool) -> dict:
+    """call(io) fills a kpe_report_rows; caps None: count first, then exactly that much."""
+    if caps is None:
+        io = ReportRows()
+        call(io)
+        caps = (io.mask_total, io.cond_total, io.pattern_total)
+    cm, cc, cp = (int(x) for x in caps)
+    v = np.zeros((nrows, R), dtype=np.uint8)
+    a = {"mask_cells": np.zeros(cm, dtype=np.uint64), "mask_words": np.zeros(cm, dtype=np.uint32),
+         "cond_cells": np.zeros(cc, dtype=np.uint64), "cond_words": np.zeros((cc, CTRACE_WORDS), dtype=np.uint32),
+         "pattern_cells": np.zeros(cp, dtype=np.uint64),
+         "pattern_traces": np.zeros((cp if records else 0, TRACE_ROOTS, TRACE_WORDS), dtype=np.uint32)}
+
+    def p(name, n):
+        return a[name].ctypes.data if n else None
+
+    io = ReportRows(v.ctypes.data if (records and v.size) else None,
+                    p("mask_cells", cm), p("mask_words", cm), cm, p("cond_cells", cc), p("cond_words", cc), cc,
+                    p("pattern_cells", cp), p("pattern_traces", cp if records else 0), cp, 0, 0, 0)
+    call(io)
+    km, kc, kp = min(io.mask_total, cm), min(io.cond_total, cc), min(io.pattern_total, cp)
+    out = {"verdict_rows": v, "mask_cells": a["mask_cells"][:km], "mask_words": a["mask_words"][:km],
+           "cond_cells": a["cond_cells"][:kc], "cond_words": a["cond_words"][:kc],
+           "pattern_cells": a["pattern_cells"][:kp], "pattern_traces": a["pattern_traces"][:kp if records else 0],
+           "mask_total": int(io.mask_total), "cond_total": int(io.cond_total), "pattern_total": int(io.pattern_total)}
+    return out
+
+
+def report_detail_need(ps: PolicySet):
+    """Which cells' report entries need which detail (kpe_report_detail_need): three (R,) uint8 arrays
+    of SEL(v) bits per rule, (mask_sel, cond_sel, pattern_sel)."""
+    R = ps.num_rules
+    t = [np.zeros(max(R, 1), dtype=np.uint8) for _ in range(3)]
+    check(load().kpe_report_detail_need(ps.h, t[0].ctypes.data, t[1].ctypes.data, t[2].ctypes.data))
+    return tuple(x[:R] for x in t)
+
+
+def report_cells(ps: PolicySet, verdict_rows, cv_mask_rows=None, cond_ex_rows=None, masks=True, cond=True, patterns=True,
+                 caps=None) -> dict:
+    """Engine.fetch_report_rows' selection over dense rows the caller holds (kpe_report_cells_host,
+    the plain double loop; no device call): verdict_rows (k, R), cv_mask_rows (k, R) raw mask words,
+    cond_ex_rows (k, R, KPE_CTRACE_WORDS). The same dict; pattern_traces is empty (there are no
+    records without a device) and verdict_rows is the input. A kind without its input is not
+    selected."""
+    R = ps.num_rules
+    v = np.ascontiguousarray(verdict_rows, dtype=np.uint8).reshape(-1, R) if R else np.zeros((0, 0), dtype=np.uint8)
+    k = v.shape[0]
+    m = None if cv_mask_rows is None else np.ascontiguousarray(cv_mask_rows, dtype=np.uint32).reshape(k, R)
+    cx = None if cond_ex_rows is None else np.ascontiguousarray(cond_ex_rows, dtype=np.uint32).reshape(k, R, CTRACE_WORDS)
+    flags = _rr_flags(masks and m is not None, cond and cx is not None, patterns)
+
+    def call(io):
+        check(load().kpe_report_cells_host(ps.h, k, v.ctypes.data if v.size else None, _ptr(m) if v.size else None,
+                                           _ptr(cx) if v.size else None, flags, ctypes.byref(io)))
+
+    out = _rr_two_calls(call, k, R, caps, records=False)
+    out["verdict_rows"] = v
+    return out
+
+
+def render_report_rows(ps: PolicySet, sparse: dict, resources=None, corpus: Optional[Corpus] = None, raw=False):
+    """The PolicyReport results of every row of a fetch_report_rows / report_cells dict in one
+    multi-threaded call (kpe_report_results_rows): a list of result lists, one per row, each what
+    report_results gives for the row's dense inputs. resources: aligned with the rows, dicts or JSON
+    bytes (None entries, or None: no messages); corpus: for pattern and foreach messages. raw: the
+    rows' JSON bytes instead of parsed lists."""
+    R = ps.num_rules
+    v = np.ascontiguousarray(sparse["verdict_rows"], dtype=np.uint8).reshape(-1, R) if R else np.zeros((0, 0), np.uint8)
+    k = v.shape[0]
+    arr = {n: np.ascontiguousarray(sparse[n], dtype=dt) for n, dt in
+           (("mask_cells", np.uint64), ("mask_words", np.uint32), ("cond_cells", np.uint64), ("cond_words", np.uint32),
+            ("pattern_cells", np.uint64), ("pattern_traces", np.uint32))}
+    km, kc = arr["mask_cells"].size, arr["cond_cells"].size
+    kp = min(arr["pattern_cells"].size, arr["pattern_traces"].size // (TRACE_ROOTS * TRACE_WORDS))
+
+    def p(name, n):
+        return arr[name].ctypes.data if n else None
+
+    io = ReportRows(v.ctypes.data if v.size else None, p("mask_cells", km), p("mask_words", km), km,
+                    p("cond_cells", kc), p("cond_words", kc), kc, p("pattern_cells", kp), p("pattern_traces", kp), kp,
+                    km, kc, kp)
+    res_p = lens = None
+    keep = []
+    if resources is not None:
+        if len(resources) != k:
+            raise ValueError("resources: one entry (or None) per row")
+        keep = [None if r is None else (bytes(r) if isinstance(r, (bytes, bytearray)) else json.dumps(r).encode())
+                for r in resources]
+        res_p = (ctypes.c_char_p * max(k, 1))(*keep)
+        lens = (ctypes.c_size_t * max(k, 1))(*[0 if r is None else len(r) for r in keep])
+    offs = np.zeros(k + 1, dtype=np.uint64)
+    cap = 1 << 16
+    while True:
+        buf = ctypes.create_string_buffer(cap)
+        n = load().kpe_report_results_rows(ps.h, corpus.h if corpus is not None else None, k, ctypes.byref(io), res_p,
+                                           lens, buf, cap, offs.ctypes.data)
+        if n < 0:
+            check(-n)
+        if n < cap:
+            break
+        cap = n + 1
+    data = buf.raw[:n]
+    parts = [data[int(offs[i]):int(offs[i + 1])] for i in range(k)]
+    return parts if raw else [json.loads(x.decode()) for x in parts]
 
 
 SEL_RESPONSES = 0xFE  # include/kpe.h KPE_SEL_RESPONSES: every verdict code but KPE_NA

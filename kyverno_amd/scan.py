@@ -130,8 +130,12 @@ class ResidentScanner:
 
     MESSAGE_CODES = SEL(2) | SEL(4) | SEL(5)  # FAIL, ERROR, SKIP: results whose message the policy text decides
 
-    def __init__(self, engine, ndjson: bytes, ns_labels=None, keep="matrix", fingerprints=None, edits=None):
-        """keep="matrix" (the default): the last verdict matrix stays on the device (N x R bytes) and
+    def __init__(self, engine, ndjson: bytes, ns_labels=None, keep="matrix", fingerprints=None, edits=None,
+                 reports=False):
+        """reports=True: the scanner keeps the NDJSON lines and evaluates with check masks, so that
+        `reports(rows)` can render the PolicyReport results of rows of the last applied PolicySet.
+
+        keep="matrix" (the default): the last verdict matrix stays on the device (N x R bytes) and
         the comparison is exact. keep="fingerprints": 8 bytes per row stay (Engine.keep_fingerprints;
         two different result sets of a row collide with probability 2^-64), they do not depend on
         the rule order, and they can be saved (`fingerprints()`, `edits`) and given back
@@ -146,6 +150,9 @@ class ResidentScanner:
         nsl = json.dumps(ns_labels).encode() if isinstance(ns_labels, dict) else ns_labels
         self.corpus = Corpus(ndjson, nsl).upload(engine.device)
         self._policies = None  # the PolicySet of the kept result (held while its matrix is kept)
+        self._with_reports = bool(reports)
+        self._lines = ndjson_rows(ndjson) if reports else None  # row i of the corpus is line i
+        self._applied = None  # the PolicySet of the last apply (what `reports` renders)
         self.edits = dict(edits or {})  # policy name -> edits seen (keep="fingerprints": folded into msg_salts)
         if fingerprints is not None:
             engine.load_fingerprints(self.corpus, fingerprints)
@@ -163,7 +170,8 @@ class ResidentScanner:
         msg = rule_salts(policies)
         for r, n in enumerate(policies.rule_names):
             msg[r] ^= np.uint64(self.edits.get(n.split("/", 1)[0], 0))
-        eng.evaluate_async(policies, corpus)
+        eng.evaluate_async(policies, corpus, masks=self._with_reports)
+        self._applied = policies
         if eng.kept_fingerprints(corpus, 0, 0) is None:
             # nothing to compare with: against "no report" (fingerprint 0), every row that has a response
             eng.load_fingerprints(corpus, np.zeros(corpus.n, dtype=np.uint64))
@@ -181,7 +189,8 @@ class ResidentScanner:
         if self.keep == "fingerprints":
             return self._apply_fp(policies, edited)
         eng, corpus = self.engine, self.corpus
-        eng.evaluate_async(policies, corpus)
+        eng.evaluate_async(policies, corpus, masks=self._with_reports)
+        self._applied = policies
         if self._policies is None:
             v, _, _ = eng.fetch(policies, corpus)  # nothing to compare with: the whole matrix, once
             out = {int(i): v[i].copy() for i in np.flatnonzero((v != 0).any(axis=1))}
@@ -196,3 +205,15 @@ class ResidentScanner:
         self._policies = policies
         self.last_stats = {"rows": corpus.n, "changed": total}
         return out
+
+    def reports(self, rows):
+        """{row: PolicyReport results} of the listed rows under the last applied PolicySet, with
+        messages (Engine.report_rows: one sparse fetch of what the rows' entries need, one bulk
+        render). Needs reports=True; typically called with the rows `apply` returned."""
+        if not self._with_reports:
+            raise KpeError(5, "ResidentScanner(reports=True) keeps what reports() needs")  # KPE_E_STATE
+        if self._applied is None:
+            raise KpeError(5, "no apply yet")
+        rows = [int(i) for i in rows]
+        res = self.engine.report_rows(self._applied, self.corpus, rows, resources=[self._lines[i] for i in rows])
+        return dict(zip(rows, res))
