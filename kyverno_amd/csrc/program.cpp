@@ -2581,7 +2581,11 @@ class Lowerer {
       }
     }
     const JV* v = r.get("validate");
-    bool has_validate = nonempty(v);
+    // HasValidate (api/kyverno/v1/rule_types.go:164-166) is !DeepEqual(Validation, Validation{}): the raw
+    // pattern / anyPattern is a pointer, non-nil whenever the member is there and not null, whatever it
+    // holds (a pattern whose every leaf is false, 0, "" or null is still a pattern)
+    auto raw_json = [&](const char* k) { return v && v->t == JV::Obj && v->get(k) && v->get(k)->t != JV::Null; };
+    bool has_validate = nonempty(v) || raw_json("pattern") || raw_json("anyPattern");
     const JV* ps = v ? v->get("podSecurity") : nullptr;
     std::string rname = sv(r.get("name"));
     // preconditions (engine.go:278-285): folded at compile time, else evaluated per resource by

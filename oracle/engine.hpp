@@ -822,7 +822,10 @@ inline Rule compile_rule(const JPtr& raw) {
   r.match = parse_match(raw->get("match"));
   r.exclude = parse_match(raw->get("exclude"));
   const JVal* v = raw->get("validate");
-  r.has_validate = jnonempty(v);
+  // rule_types.go:164-166 !DeepEqual(Validation, Validation{}): RawPattern / RawAnyPattern are pointers,
+  // non-nil for any member that is not null, so a pattern of zero values only is a validate rule too
+  auto raw_json = [&](const char* k) { return v && v->t == JT::Obj && v->get(k) && !v->get(k)->is_null(); };
+  r.has_validate = jnonempty(v) || raw_json("pattern") || raw_json("anyPattern");
   const JVal* ps = v ? v->get("podSecurity") : nullptr;
   if (v && jnonempty(v->get("manifests"))) r.unsupported = true;
   else if (ps && ps->t == JT::Obj && jnonempty(ps)) {

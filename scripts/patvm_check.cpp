@@ -199,7 +199,7 @@ int main(int argc, char** argv) {
   FILE* f = fopen(argv[3], "wb");
   fwrite(verdicts.data(), 1, (size_t)C.n * R, f);
   fclose(f);
-  printf("%lld %u err=0x%x\n", (long long)C.n, R, err);
+  printf("%lld %u err=0x%x nscal=%zu\n", (long long)C.n, R, err, scal.size());
   if (err) return 1;
   return 0;
 }
