@@ -318,6 +318,7 @@ struct LeanBatchArgs {
   // the first KPE_L6_CLS version classes as evidence masks (below; zero past ncls): a pod fails
   // class c when its evidence word meets ev[c], or ev_nw[c] on a pod that is not a Windows pod
   uint32_t cls_ev[4], cls_ev_nw[4], cls_rm[4];
+  const uint32_t* pod_tab;  // kpe_l6_pod_table_word(0 .. KPE_L6_PT_WORDS - 1): one copy per device
   uint32_t blk0[KPE_LEAN_BATCH + 1];  // a block covers 4 * tpw tiles of 64 pods
   LeanShard sh[KPE_LEAN_BATCH];
 };
@@ -327,6 +328,9 @@ struct LeanBatchArgs {
 #define KPE_L6_VOL 128u
 #define KPE_L6_SMALL 64u
 #define KPE_L6_STAGE_BYTES (KPE_L6_CTR * 4u + KPE_L6_VOL + 2u * KPE_L6_SMALL)
+// A pod ORs its first four containers with four dword reads from its first slot on: the reads of
+// a pod whose containers end at slot KPE_L6_CTR - 1 reach 12 bytes into the volume bytes that
+// follow (read, never selected: a word past the pod's count is dropped).
 // A staged container: the state bits the PSA checks read (CX_*, in place) with the container's
 // codes in bits those leave free: its capability-set code (CS_* of scan.hip) and whether its
 // seccomp annotation is outside the allowed profiles. The word of an empty slot is 0.
@@ -348,6 +352,53 @@ struct LeanBatchArgs {
 #define KPE_L6_EV_HOSTNS (1u << 6)
 #define KPE_L6_VOL_SH 13           // volume code: bit 0 hostPath, bit 1 outside the restricted set
 #define KPE_L6_ANN_SH 17           // annotation code: bit 0 AppArmor, bit 1 pod seccomp annotation
+#if defined(__HIPCC__)
+#define KPE_L6_FN __host__ __device__ inline
+#else
+#define KPE_L6_FN static inline
+#endif
+// The pod word's part of the evidence word: bits to set and container bits to clear.
+KPE_L6_FN void kpe_l6_pod_evidence(uint32_t pw, uint32_t* set, uint32_t* clr) {
+  const uint32_t prnr = FIELD(pw, P_RNR_SH, 2), psel = FIELD(pw, P_SEL_SH, 3), psec = FIELD(pw, P_SECCOMP_SH, 3);
+  const uint32_t kSecValid = (1u << SECCOMP_RUNTIMEDEFAULT) | (1u << SECCOMP_LOCALHOST);
+  const uint32_t kSecBad = 0xFFu & ~kSecValid & ~(1u << SECCOMP_NONE);
+  const bool sel_bad = psel != SEL_NONE && (psel == SEL_OTHER || (pw & (P_SEL_USER | P_SEL_ROLE)));
+  *set = ((pw & (P_HOSTNET | P_HOSTPID | P_HOSTIPC)) ? KPE_L6_EV_HOSTNS : 0u) | (prnr == TRI_FALSE ? CX_RNR_F : 0u) |
+         (FIELD(pw, P_RAU_SH, 2) == RAU_ZERO ? CX_RAU_Z : 0u) | (sel_bad ? CX_SEL_OTHER : 0u) |
+         (((kSecBad >> psec) & 1u) ? CX_SEC_UNC : 0u) | (FIELD(pw, P_WHP_SH, 2) == TRI_TRUE ? CX_WHP_T : 0u);
+  *clr = (prnr == TRI_TRUE ? CX_RNR_U : 0u) | (((kSecValid >> psec) & 1u) ? CX_SEC_NONE : 0u);
+}
+// Checks marked *nw below apply to a pod unless it is a Windows pod.
+KPE_L6_FN bool kpe_l6_not_windows(uint32_t pw) { return FIELD(pw, P_OS_SH, 2) != OS_WINDOWS; }
+// The same from a constant table (verdict-only evaluations): every field above lies in bits 1-19
+// of the pod word and contributes on its own (the SELinux type with its user / role bits), so
+// the pod's bits are the OR of one entry per slice of the pod word: bits 1-7, 8-15 and 16-19.
+// An entry holds its slice's set bits, its clear bits (KPE_L6_PT_CLR: no field sets those) and,
+// in the slice that holds the OS field, KPE_L6_PT_NW for a pod that is not a Windows pod. Built
+// once per device (policy- and corpus-independent) and copied to LDS by every block.
+#define KPE_L6_PT_B0 128u   // first entry of the second slice
+#define KPE_L6_PT_C0 384u   // first entry of the third slice
+#define KPE_L6_PT_WORDS 400u
+#define KPE_L6_PT_CLR (CX_RNR_U | CX_SEC_NONE)
+#define KPE_L6_PT_NW (1u << 31)
+KPE_L6_FN uint32_t kpe_l6_pod_table_word(uint32_t i) {
+  const uint32_t pw = i < KPE_L6_PT_B0 ? i << 1 : i < KPE_L6_PT_C0 ? (i - KPE_L6_PT_B0) << 8 : (i - KPE_L6_PT_C0) << 16;
+  uint32_t set, clr;
+  kpe_l6_pod_evidence(pw, &set, &clr);
+  return set | clr | (i >= KPE_L6_PT_C0 && kpe_l6_not_windows(pw) ? KPE_L6_PT_NW : 0u);
+}
+// tab: the table (LDS, or host memory in the checks); the result is split by kpe_l6_pod_split
+KPE_L6_FN uint32_t kpe_l6_pod_lookup(const uint32_t* tab, uint32_t pw) {
+  return tab[(pw >> 1) & 127u] | tab[KPE_L6_PT_B0 + ((pw >> 8) & 255u)] | tab[KPE_L6_PT_C0 + ((pw >> 16) & 15u)];
+}
+// The evidence word of a pod from the OR of its containers (cw), the table word and its list bits.
+KPE_L6_FN uint32_t kpe_l6_pod_split(uint32_t cw, uint32_t tw, uint32_t lists) {
+  return (cw & ~(tw & KPE_L6_PT_CLR)) | (tw & ~(KPE_L6_PT_CLR | KPE_L6_PT_NW)) | lists;
+}
+// The OR of a pod's first min(nc, 4) staged containers from the four words at its first slot on.
+KPE_L6_FN uint32_t kpe_l6_ctr_or(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t nc) {
+  return (nc > 0u ? x0 : 0u) | (nc > 1u ? x1 : 0u) | (nc > 2u ? x2 : 0u) | (nc > 3u ? x3 : 0u);
+}
 // Evidence bits of versioned check cv; *nw: the check does not apply to Windows pods.
 static inline uint32_t kpe_l6_evidence(uint32_t cv, bool* nw) {
   *nw = cv == CV_APE_1_25 || cv == CV_CAPS_RESTRICTED_1_25 || cv == CV_SECCOMP_RESTRICTED_1_25;
@@ -377,6 +428,22 @@ static inline uint32_t kpe_l6_evidence(uint32_t cv, bool* nw) {
     case CV_WIN_HOST_PROCESS_1_0: return CX_WHP_T;
     default: return 0u;
   }
+}
+// The masks of a version class with the versioned checks `checks` (LeanBatchArgs::cls_ev,
+// cls_ev_nw): a pod fails the class when its evidence word meets ev, or ev_nw on a pod that is
+// not a Windows pod.
+struct KpeL6ClassMasks {
+  uint32_t ev, ev_nw;
+};
+static inline KpeL6ClassMasks kpe_l6_class_masks(uint32_t checks) {
+  KpeL6ClassMasks m = {0u, 0u};
+  for (uint32_t v = 0; v < KPE_NUM_CV; ++v) {
+    if (!((checks >> v) & 1u)) continue;
+    bool nw;
+    const uint32_t ev = kpe_l6_evidence(v, &nw);
+    (nw ? m.ev_nw : m.ev) |= ev;
+  }
+  return m;
 }
 
 // kpe_pattern_kernel arguments (device-resident, one copy per binding)

@@ -137,6 +137,9 @@ struct kpe_device {
   bool no_psum = true;
   uint64_t lean_min_waves = 16384;  // 256 CUs x 4 SIMDs x 16 waves
   uint32_t lean_tpw = 0, lean_shape = 0;
+  // kpe_lean6_kernel's pod-evidence table (kernels_abi.h kpe_l6_pod_table_word), built at
+  // kpe_device_open: it depends on neither the policies nor a corpus
+  DevBuf lean_pod_tab;
   // pinned staging for corpus uploads (two halves, double-buffered; allocated on first use): a
   // pageable hipMemcpyAsync is staged by the runtime chunk by chunk, a pinned one is one DMA
   static constexpr size_t kStageHalf = 16u << 20;
@@ -340,6 +343,16 @@ kpe_status kpe_device_open(int ordinal, kpe_device** out) {
     }
   }
   d->stream = d->lanes[0];
+  {
+    uint32_t tab[KPE_L6_PT_WORDS];
+    for (uint32_t i = 0; i < KPE_L6_PT_WORDS; ++i) tab[i] = kpe_l6_pod_table_word(i);
+    e = d->lean_pod_tab.ensure(sizeof(tab));
+    if (e == hipSuccess) e = hipMemcpy(d->lean_pod_tab.p, tab, sizeof(tab), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      kpe_device_close(d);
+      return fail(KPE_E_DEVICE, hipGetErrorString(e));
+    }
+  }
   *out = d;
   return KPE_OK;
 }
@@ -1898,15 +1911,12 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
   const bool cv = masks || PD.ncls > KPE_L6_CLS || (dev->lean_shape & 2u);
   if (!cv)
     for (uint32_t c = 0; c < PD.ncls; ++c) {
-      const uint32_t checks = PD.cls_h[2 * c] & P.cv_union;
-      for (uint32_t v = 0; v < KPE_NUM_CV; ++v) {
-        bool nw;
-        const uint32_t ev = kpe_l6_evidence(v, &nw);
-        if ((checks >> v) & 1u) (nw ? a.cls_ev_nw : a.cls_ev)[c] |= ev;
-      }
+      const KpeL6ClassMasks m = kpe_l6_class_masks(PD.cls_h[2 * c] & P.cv_union);
+      a.cls_ev[c] = m.ev, a.cls_ev_nw[c] = m.ev_nw;
       a.cls_rm[c] = PD.cls_h[2 * c + 1];
     }
-  const size_t dyn = 4 * ((size_t)a.kt_words + a.code_words + 4 * (size_t)a.wave_words);
+  a.pod_tab = dev->lean_pod_tab.as<uint32_t>();
+  const size_t dyn = 4 * ((size_t)KPE_L6_PT_WORDS + a.kt_words + a.code_words + 4 * (size_t)a.wave_words);
   HIPCHK(kpe_launch_lean6(&a, dyn, lc ? 1 : 0, (a.need & NEED_SANN) || (dev->lean_shape & 1u) ? 1 : 0, cv ? 1 : 0, s));
   return KPE_OK;
 }

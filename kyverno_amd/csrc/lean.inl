@@ -36,6 +36,14 @@ __device__ __forceinline__ const __attribute__((address_space(4))) void* kargs()
 #ifndef KPE_LEAN6_WAVES
 #define KPE_LEAN6_WAVES 6
 #endif
+// Scalar registers of the kernel: a CU holds seven 256-thread blocks up to 96 of them and six
+// above (800 per SIMD in blocks of 16, 16 more per wave), and the compiler takes all it may.
+// The cap holds for every instantiation: the C2 one (<4, true, false, false>) fits in 94 without
+// a spill; <4, true, true, false> (seccomp annotations, verdicts only) spills two scalars into
+// lanes under it, the others none.
+#ifndef KPE_LEAN6_SGPRS
+#define KPE_LEAN6_SGPRS 96
+#endif
 constexpr uint32_t kLB = 256;
 // XCD-aware block order: the dispatcher deals workgroups round-robin to the 8 XCDs (block b on
 // XCD b % 8), so block b takes the (b / 8)-th block of XCD b % 8's contiguous share of the tiles:
@@ -222,7 +230,9 @@ __global__ void __launch_bounds__(256) kpe_psum_kernel(PsumArgs a) {
 // How a class is decided is the CV parameter. CV: every versioned check (cv_fails), masked by the
 // class's checks; needed for the check masks per cell (LeanShard::masks) and taken by programs of
 // more than KPE_L6_CLS classes. Otherwise (verdicts only): one AND of the pod's evidence word
-// with the class's evidence mask (LeanBatchArgs::cls_ev). Both give the same verdicts.
+// with the class's evidence mask (LeanBatchArgs::cls_ev), the pod word's part of that word read
+// from a constant table every block copies to LDS ahead of its kind table (kernels_abi.h
+// kpe_l6_pod_table_word). Both give the same verdicts.
 typedef const __attribute__((address_space(4))) LeanBatchArgs CBArgs;
 typedef const __attribute__((address_space(4))) LeanShard CShard;
 template <bool SANN>
@@ -236,22 +246,12 @@ template <>
 struct L6Items<true> : L6Items<false> {
   uint32_t a0, a1;
 };
-// The pod word's part of the evidence word: bits to set and container bits to clear.
-__device__ __forceinline__ void l6_pod_evidence(uint32_t pw, uint32_t& set, uint32_t& clr) {
-  const uint32_t prnr = FIELD(pw, P_RNR_SH, 2), psel = FIELD(pw, P_SEL_SH, 3), psec = FIELD(pw, P_SECCOMP_SH, 3);
-  constexpr uint32_t kSecValid = (1u << SECCOMP_RUNTIMEDEFAULT) | (1u << SECCOMP_LOCALHOST);
-  constexpr uint32_t kSecBad = 0xFFu & ~kSecValid & ~(1u << SECCOMP_NONE);
-  const bool sel_bad = psel != SEL_NONE && (psel == SEL_OTHER || (pw & (P_SEL_USER | P_SEL_ROLE)));
-  set = ((pw & (P_HOSTNET | P_HOSTPID | P_HOSTIPC)) ? KPE_L6_EV_HOSTNS : 0u) | (prnr == TRI_FALSE ? CX_RNR_F : 0u) |
-        (FIELD(pw, P_RAU_SH, 2) == RAU_ZERO ? CX_RAU_Z : 0u) | (sel_bad ? CX_SEL_OTHER : 0u) |
-        (((kSecBad >> psec) & 1u) ? CX_SEC_UNC : 0u) | (FIELD(pw, P_WHP_SH, 2) == TRI_TRUE ? CX_WHP_T : 0u);
-  clr = (prnr == TRI_TRUE ? CX_RNR_U : 0u) | (((kSecValid >> psec) & 1u) ? CX_SEC_NONE : 0u);
-}
 // sysctl code (bit v: outside version v's set) at its evidence bits
 __device__ __forceinline__ uint32_t l6_sys_evidence(uint32_t c) { return ((c & 3u) << 1) | ((c & 4u) << 2); }
 
 template <int T, bool LC, bool SANN, bool CV>
-__global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBatchArgs) {
+__global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) __attribute__((amdgpu_num_sgpr(KPE_LEAN6_SGPRS)))
+kpe_lean6_kernel(LeanBatchArgs) {
   extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
   CBArgs& a = *(CBArgs*)kargs();
   const uint32_t t = threadIdx.x, lane = t & 63u;
@@ -286,6 +286,14 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
   const uint32_t ncw = LC ? (S.L.bytes + 3u) >> 2 : 0u;
   const uint32_t* gcw = reinterpret_cast<const uint32_t*>(S.codes);
   const uint32_t cw0 = LC && t < ncw ? gcw[t] : 0u;
+  // (verdicts only) the pod-evidence table, ahead of the kind table
+  constexpr bool PT = !CV;
+  uint32_t pt0 = 0, pt1 = 0;
+  if constexpr (PT) {
+    const uint32_t* const gpt = a.pod_tab;
+    pt0 = gpt[t];
+    pt1 = t < KPE_L6_PT_WORDS - kLB ? gpt[t + kLB] : 0u;
+  }
   // ---- step 2: the list items of every tile
   L6Items<SANN> it[T];
 #pragma unroll
@@ -304,10 +312,15 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
     it[j].s0 = bload1(SYS, (S0 + lane) * 4u);
     it[j].q0 = bload2(ANN, (A0 + lane) * 8u);
   }
-  if (t < nk) dyn[t] = k0;
+  if constexpr (PT) {
+    dyn[t] = pt0;
+    if (t < KPE_L6_PT_WORDS - kLB) dyn[t + kLB] = pt1;
+  }
+  uint32_t* const kt = dyn + KPE_L6_PT_WORDS;
+  if (t < nk) kt[t] = k0;
 #pragma unroll 1
-  for (uint32_t i = t + kLB; i < nk; i += kLB) dyn[i] = S.kt[i];
-  uint32_t* const cl = dyn + a.kt_words;
+  for (uint32_t i = t + kLB; i < nk; i += kLB) kt[i] = S.kt[i];
+  uint32_t* const cl = kt + a.kt_words;
   if (LC) {
     if (t < ncw) cl[t] = cw0;
 #pragma unroll 1
@@ -328,6 +341,9 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
   L.o_sys = S.L.o_sys, L.o_annk = S.L.o_annk, L.o_annv = S.L.o_annv, L.bytes = S.L.bytes;
   const PsaCoder K{L};
   const bool nvol = need & NEED_VOL, nsys = need & NEED_SYS, npann = need & NEED_PANN;
+  // item counts above which a pod takes the slow path, as scalars: a list the program does not
+  // read has a limit no byte count exceeds
+  const uint32_t lim_v = nvol ? 4u : 255u, lim_s = nsys ? 2u : 255u, lim_a = npann ? 2u : 255u;
   // a container's stage word (a real record always has state bits, tested before they are masked)
   auto ctr_word = [&](uint2 e, uint32_t cs) -> uint32_t {
     uint32_t w = (e.x & KPE_L6_CX_USED) | ((cb(CY_CAPSET(e.y)) & 7u) << KPE_L6_CAP_SH);
@@ -403,9 +419,10 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
     // each pod ORs its first items with clamped reads (a repeated item does not change an OR)
     uint32_t cw, vcode = 0, scode = 0, acode = 0;
     {
-      const uint32_t last = min(oc + (nc ? nc - 1u : 0u), KPE_L6_CTR - 1u);
-      const uint32_t x = sc[min(oc, last)] | sc[min(oc + 1u, last)] | sc[min(oc + 2u, last)] | sc[min(oc + 3u, last)];
-      cw = nc ? x : 0u;
+      // containers: four words from the pod's first slot on (one address; a pod whose containers
+      // reach past the stage is recomputed below, and the reads of slot 127 end in the volume bytes)
+      const uint32_t* const p = sc + min(oc, KPE_L6_CTR - 1u);
+      cw = kpe_l6_ctr_or(p[0], p[1], p[2], p[3], nc);
     }
     if (nvol) {
       const uint32_t last = min(ov + (nv ? nv - 1u : 0u), KPE_L6_VOL - 1u);
@@ -427,7 +444,7 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
     // (staged ones from LDS, the rest loaded)
     const bool tile_over = nct > KPE_L6_CTR || (nvol && nvt > KPE_L6_VOL) || (nsys && nst > KPE_L6_SMALL) ||
                            (npann && nat > KPE_L6_SMALL);
-    const bool more_c = nc > 4u, more_v = nvol && nv > 4u, more_s = nsys && ns > 2u, more_a = npann && na > 2u;
+    const bool more_c = nc > 4u, more_v = nv > lim_v, more_s = ns > lim_s, more_a = na > lim_a;
     if (tile_over || __builtin_amdgcn_ballot_w64(more_c || more_v || more_s || more_a)) {
       if (more_c || oc + nc > KPE_L6_CTR) {
         cw = 0;
@@ -467,20 +484,28 @@ __global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) kpe_lean6_kernel(LeanBat
         for (uint32_t c = 0; c < ncls; ++c) failr |= (fails & hw(cls_cv, c)) ? hw(cls_rm, c) : 0u;
       }
     } else {
-      uint32_t set, clr;
-      l6_pod_evidence(pw, set, clr);
-      const uint32_t ev = (cw & ~clr) | set | (vcode << KPE_L6_VOL_SH) | scode | (acode << KPE_L6_ANN_SH);
-      const uint32_t nwin = FIELD(pw, P_OS_SH, 2) == OS_WINDOWS ? 0u : ~0u;
+      const uint32_t lists = (vcode << KPE_L6_VOL_SH) | scode | (acode << KPE_L6_ANN_SH);
+      // the pod word's part from the table: three LDS reads at constant offsets
+      const uint32_t tw = kpe_l6_pod_lookup(dyn, pw);
+      const uint32_t ev = kpe_l6_pod_split(cw, tw, lists);
+      const uint32_t ev_nw = ev & (uint32_t)((int32_t)tw >> 31);  // KPE_L6_PT_NW over the word
 #pragma unroll
       for (uint32_t c = 0; c < KPE_L6_CLS; ++c) {
         if (c >= ncls) break;
-        failr |= (ev & (cev[c] | (cev_nw[c] & nwin))) ? crm[c] : 0u;
+        const uint32_t hit = (ev & cev[c]) | (ev_nw & cev_nw[c]);
+        uint32_t m = hit ? ~0u : 0u;
+        // Keeps the select on inline constants: as a select of crm[c] it costs a v_mov more per
+        // class. Static VALU of <4, true, false, false> in the build this was measured in: 1,523
+        // without the empty asm, 1,511 with it, nothing else changed. Harmless if a
+        // later compiler no longer needs it; drop it if those two counts come out equal.
+        asm("" : "+v"(m));
+        failr |= m & crm[c];
       }
     }
     const uint32_t cls = (pw >> PR_CLASS_SH) & R_CLASS_MASK;
     const bool err = cls == R_CLASS_OTHER || (pw & PR_DECODE_ERR);
     const uint32_t kind = GVK_KIND(rec[j].y);
-    const uint32_t matched = live && kind < nk ? dyn[kind] : 0u;
+    const uint32_t matched = live && kind < nk ? kt[kind] : 0u;
     const uint32_t E = matched & ((err ? pss_rules : 0u) | ep_rules);
     const uint32_t F = (matched & pss_rules & failr & ~E) | (matched & pat_rules);  // F|E = PENDING
     const uint32_t P = matched & pss_rules & ~failr & ~E;
