@@ -304,7 +304,8 @@ struct SelMaskArgs {
 #define KPE_LEAN_BATCH 24
 struct LeanShard {
   const uint32_t *rec, *hdr, *crec, *vol, *sys, *pann, *sann;  // the corpus's PSS columns
-  const uint8_t* codes;   // the corpus's PSA dictionary codes (PsaCodeArgs::codes)
+  const uint32_t *rec12, *cw4;  // its compact columns (below: 12-byte pod records, container words)
+  const uint8_t* codes;  // the corpus's PSA dictionary codes (PsaCodeArgs::codes)
   const uint32_t* kt;     // the binding's kind table: matched-rule mask per kind id (prologue image)
   uint8_t* verdicts;      // n x R
   uint32_t* masks;        // n x R failing versioned checks, or null
@@ -318,10 +319,13 @@ struct LeanBatchArgs {
   // the first KPE_L6_CLS version classes as evidence masks (below; zero past ncls): a pod fails
   // class c when its evidence word meets ev[c], or ev_nw[c] on a pod that is not a Windows pod
   uint32_t cls_ev[4], cls_ev_nw[4], cls_rm[4];
-  const uint32_t* pod_tab;  // kpe_l6_pod_table_word(0 .. KPE_L6_PT_WORDS - 1): one copy per device
+  // kpe_l6_pod_table_word(0 .. KPE_L6_PT_WORDS - 1), one copy per device; a launch that reads the
+  // compact columns gets the table and the class masks above in the packed numbering (kpe_l6_pack_ev)
+  const uint32_t* pod_tab;
   uint32_t blk0[KPE_LEAN_BATCH + 1];  // a block covers 4 * tpw tiles of 64 pods
   LeanShard sh[KPE_LEAN_BATCH];
 };
+static_assert(sizeof(LeanBatchArgs) < 4096, "LeanBatchArgs is passed by value: under 4 KiB of kernel arguments");
 // Per-wave LDS stage of kpe_lean6_kernel: a tile's staged list items (one word per container,
 // volume / sysctl / annotation codes as bytes); items past these counts are loaded again.
 #define KPE_L6_CTR 128u
@@ -354,9 +358,63 @@ struct LeanBatchArgs {
 #define KPE_L6_ANN_SH 17           // annotation code: bit 0 AppArmor, bit 1 pod seccomp annotation
 #if defined(__HIPCC__)
 #define KPE_L6_FN __host__ __device__ inline
+#define KPE_L6_FORCE __host__ __device__ __forceinline__
 #else
 #define KPE_L6_FN static inline
+#define KPE_L6_FORCE static inline
 #endif
+// Capability-set violation bits (computed per block into LDS from the capset dictionary)
+#define CS_BASE 1u  // add has a capability outside the baseline allow-list
+#define CS_DROP 2u  // drop lacks "ALL" (also: no capabilities at all)
+#define CS_ADD 4u   // add has anything but NET_BIND_SERVICE
+
+// PSA versioned checks for one pod (PSA v0.29 policy/check_*.go, restated in
+// oracle/pss.hpp) from the pod word and the OR of its containers' state bitmaps.
+// "Containers" = initContainers + containers + ephemeralContainers.
+KPE_L6_FORCE uint32_t cv_fails(uint32_t pw, uint32_t xo, uint32_t co, bool sec_ann_bad,
+                                             bool vol_hostpath, bool vol_restricted, uint32_t sys_bad,
+                                             bool apparmor_bad, bool sec_pod_ann_bad) {
+  // Branch-free: every condition is a 0/1 value combined with & and | (no short circuit), so the
+  // whole function is selects and shifts on the lane.
+  auto on = [](uint32_t c, uint32_t cv) -> uint32_t { return (c ? 1u : 0u) << cv; };
+  const uint32_t nwin = FIELD(pw, P_OS_SH, 2) == OS_WINDOWS ? 0u : ~0u;
+  uint32_t f = 0;
+  // allowPrivilegeEscalation: some container whose APE is unset (or SC nil) or true
+  f |= (xo & (CX_APE_T | CX_APE_U)) ? (1u << CV_APE_1_8) | ((1u << CV_APE_1_25) & nwin) : 0u;
+  f |= on(apparmor_bad, CV_APPARMOR_1_0);
+  f |= on(co & CS_BASE, CV_CAPS_BASELINE_1_0);
+  f |= (co & (CS_DROP | CS_ADD)) ? (1u << CV_CAPS_RESTRICTED_1_22) | ((1u << CV_CAPS_RESTRICTED_1_25) & nwin) : 0u;
+  f |= on(pw & (P_HOSTNET | P_HOSTPID | P_HOSTIPC), CV_HOST_NS_1_0);
+  f |= on(vol_hostpath, CV_HOST_PATH_1_0);
+  f |= on(xo & CX_HOSTPORT, CV_HOST_PORTS_1_0);
+  f |= on(xo & CX_PRIV_T, CV_PRIVILEGED_1_0);
+  f |= on(xo & CX_PM_OTHER, CV_PROC_MOUNT_1_0);
+  f |= on(vol_restricted, CV_RESTRICTED_VOLUMES_1_0);
+  const uint32_t prnr = FIELD(pw, P_RNR_SH, 2);
+  f |= on((uint32_t)(prnr == TRI_FALSE) | (uint32_t)((xo & CX_RNR_F) != 0u) |
+              ((uint32_t)(prnr != TRI_TRUE) & (uint32_t)((xo & CX_RNR_U) != 0u)),
+          CV_RUN_AS_NON_ROOT_1_0);
+  f |= on((uint32_t)(FIELD(pw, P_RAU_SH, 2) == RAU_ZERO) | (uint32_t)((xo & CX_RAU_Z) != 0u), CV_RUN_AS_USER_1_23);
+  const uint32_t psel = FIELD(pw, P_SEL_SH, 3);
+  f |= on(((uint32_t)(psel != SEL_NONE) &
+           ((uint32_t)(psel == SEL_OTHER) | (uint32_t)((pw & (P_SEL_USER | P_SEL_ROLE)) != 0u))) |
+              (uint32_t)((xo & (CX_SEL_OTHER | CX_SEL_USER | CX_SEL_ROLE)) != 0u),
+          CV_SELINUX_1_0);
+  f |= on((uint32_t)sec_pod_ann_bad | (uint32_t)sec_ann_bad, CV_SECCOMP_BASELINE_1_0);
+  // pod seccomp type: valid = RuntimeDefault | Localhost, bad = set and not valid
+  const uint32_t psec = FIELD(pw, P_SECCOMP_SH, 3);
+  constexpr uint32_t kSecValid = (1u << SECCOMP_RUNTIMEDEFAULT) | (1u << SECCOMP_LOCALHOST);
+  constexpr uint32_t kSecBad = 0xFFu & ~kSecValid & ~(1u << SECCOMP_NONE);
+  const uint32_t psec_valid = (kSecValid >> psec) & 1u, psec_bad = (kSecBad >> psec) & 1u;
+  const uint32_t sec_b = psec_bad | (uint32_t)((xo & (CX_SEC_UNC | CX_SEC_OTHER)) != 0u);
+  f |= on(sec_b, CV_SECCOMP_BASELINE_1_19);
+  f |= (sec_b | ((psec_valid ^ 1u) & (uint32_t)((xo & CX_SEC_NONE) != 0u)))
+           ? (1u << CV_SECCOMP_RESTRICTED_1_19) | ((1u << CV_SECCOMP_RESTRICTED_1_25) & nwin)
+           : 0u;
+  f |= on(sys_bad & 1u, CV_SYSCTLS_1_0) | on(sys_bad & 2u, CV_SYSCTLS_1_27) | on(sys_bad & 4u, CV_SYSCTLS_1_29);
+  f |= on((uint32_t)(FIELD(pw, P_WHP_SH, 2) == TRI_TRUE) | (uint32_t)((xo & CX_WHP_T) != 0u), CV_WIN_HOST_PROCESS_1_0);
+  return f;
+}
 // The pod word's part of the evidence word: bits to set and container bits to clear.
 KPE_L6_FN void kpe_l6_pod_evidence(uint32_t pw, uint32_t* set, uint32_t* clr) {
   const uint32_t prnr = FIELD(pw, P_RNR_SH, 2), psel = FIELD(pw, P_SEL_SH, 3), psec = FIELD(pw, P_SECCOMP_SH, 3);
@@ -445,6 +503,69 @@ static inline KpeL6ClassMasks kpe_l6_class_masks(uint32_t checks) {
   }
   return m;
 }
+
+// ---- the compact columns (DeviceCorpus rec12 / cw4, built once per corpus by
+// kpe_lean_pack_kernel) and the packed numbering the verdict-only evaluation decides in ----------
+// rec12: words {x, y, z} of a pod record (w, the namespace id, is not read). cw4: one word per
+// container, a lossless re-packing of what the LEAN evaluation reads of its record: the
+// KPE_L6_CX_USED state bits squeezed together in ascending CX_* order (bits 0-14), the
+// capability-set id (bits 15-25) and bit 31, set for every real container: an empty slot is the
+// word 0, a container none of whose used states is set is not. No code, no evidence, nothing of
+// a policy: the codes are looked up from the id by every evaluation, as from the wide record.
+#define KPE_L6C_STATES 15u
+#define KPE_L6C_ID_SH 15
+#define KPE_L6C_ID_MASK 0x7FFu
+#define KPE_L6C_REAL (1u << 31)
+static_assert(KPE_MAX_CAPSETS <= KPE_L6C_ID_MASK + 1u, "capability-set ids past the container word's 11 bits");
+// The packed evidence word: the in-place word (above) under one fixed permutation of its bits
+// (kpe_l6_pack_ev), so every bit keeps its one definition (kpe_l6_evidence, kpe_l6_pod_evidence,
+// KPE_L6_PT_CLR) and the packed class masks and pod table are those, permuted. The staged
+// container word is (cw4 & states) | capability-set code << CAP_SH | seccomp annotation << SANN_SH.
+#define KPE_L6C_CAP_SH 15     // 3 bits, from KPE_L6_CAP_SH
+#define KPE_L6C_SANN_SH 18    // 1 bit, from KPE_L6_SANN_SH
+#define KPE_L6C_SYS_SH 19     // the sysctl code as it is: bit v from KPE_L6_EV_SYSv
+#define KPE_L6C_HOSTNS_SH 22  // from KPE_L6_EV_HOSTNS
+#define KPE_L6C_VOL_SH 23     // 2 bits, from KPE_L6_VOL_SH
+#define KPE_L6C_ANN_SH 25     // 2 bits, from KPE_L6_ANN_SH; bit 31 (KPE_L6_PT_NW) stays
+// the used state bits of cx, squeezed together in ascending order
+KPE_L6_FN uint32_t kpe_l6_pack_cx(uint32_t cx) {
+  uint32_t p = 0, k = 0;
+  for (uint32_t b = 0; b < 32u; ++b)
+    if ((KPE_L6_CX_USED >> b) & 1u) p |= ((cx >> b) & 1u) << k++;
+  return p;
+}
+KPE_L6_FN uint32_t kpe_l6_unpack_cx(uint32_t p) {
+  uint32_t cx = 0, k = 0;
+  for (uint32_t b = 0; b < 32u; ++b)
+    if ((KPE_L6_CX_USED >> b) & 1u) cx |= ((p >> k++) & 1u) << b;
+  return cx;
+}
+// the container word of a container record (cx: state bits, cy: CY_* word)
+KPE_L6_FN uint32_t kpe_l6_pack_ctr(uint32_t cx, uint32_t cy) {
+  return kpe_l6_pack_cx(cx) | ((CY_CAPSET(cy) & KPE_L6C_ID_MASK) << KPE_L6C_ID_SH) | KPE_L6C_REAL;
+}
+KPE_L6_FN uint32_t kpe_l6_ctr_capset(uint32_t w) { return (w >> KPE_L6C_ID_SH) & KPE_L6C_ID_MASK; }
+KPE_L6_FN uint32_t kpe_l6_ctr_states(uint32_t w) { return kpe_l6_unpack_cx(w & ((1u << KPE_L6C_STATES) - 1u)); }
+// an in-place evidence word, class mask or pod-table word in the packed numbering
+KPE_L6_FN uint32_t kpe_l6_pack_ev(uint32_t ev) {
+  const uint32_t sys = ((ev & KPE_L6_EV_SYS0) ? 1u : 0u) | ((ev & KPE_L6_EV_SYS1) ? 2u : 0u) | ((ev & KPE_L6_EV_SYS2) ? 4u : 0u);
+  return kpe_l6_pack_cx(ev) | (((ev >> KPE_L6_CAP_SH) & 7u) << KPE_L6C_CAP_SH) |
+         (((ev >> KPE_L6_SANN_SH) & 1u) << KPE_L6C_SANN_SH) | (sys << KPE_L6C_SYS_SH) |
+         ((ev & KPE_L6_EV_HOSTNS) ? 1u << KPE_L6C_HOSTNS_SH : 0u) | (((ev >> KPE_L6_VOL_SH) & 3u) << KPE_L6C_VOL_SH) |
+         (((ev >> KPE_L6_ANN_SH) & 3u) << KPE_L6C_ANN_SH) | (ev & KPE_L6_PT_NW);
+}
+// KPE_L6_PT_CLR packed (CX_RNR_U, CX_SEC_NONE): bits 4 and 6 of the 15 states
+#define KPE_L6C_PT_CLR 0x50u
+// kpe_l6_pod_split in the packed numbering (tw: a packed table word)
+KPE_L6_FN uint32_t kpe_l6c_pod_split(uint32_t cw, uint32_t tw, uint32_t lists) {
+  return (cw & ~(tw & KPE_L6C_PT_CLR)) | (tw & ~(KPE_L6C_PT_CLR | KPE_L6_PT_NW)) | lists;
+}
+// kpe_lean_pack_kernel: the compact columns of a corpus, one launch (threads over pods and containers)
+struct LeanPackArgs {
+  const uint32_t *rec, *crec;  // n x 4 words, nctr x 2 words
+  uint32_t *rec12, *cw4;       // out: n x 3 words, nctr words
+  uint32_t n, nctr;
+};
 
 // kpe_pattern_kernel arguments (device-resident, one copy per binding)
 struct PatArgs {

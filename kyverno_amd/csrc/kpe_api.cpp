@@ -128,7 +128,8 @@ struct kpe_device {
   // evaluation), KPE_PATVM_ERR (report a KPE_PATVM_CHECK build's bounds flags), KPE_LEAN6_MINW /
   // KPE_LEAN6_TPW (waves a LEAN6 launch keeps / tiles per wave, for A/B runs), KPE_LEAN6_SHAPE
   // (A/B runs: bit 0 the instantiation that reads the seccomp annotations, bit 1 the one that
-  // decides every versioned check, for programs that need neither)
+  // decides every versioned check, for programs that need neither; bit 4, i.e. 16: the
+  // verdict-only form reads the wide records, not the corpus's compact columns)
   bool no_cache = false, patvm_err = false;
   // the general scan of a podSecurity program walks each pod's lists itself; KPE_PSUM=1: it reads
   // per-pod records kpe_psum_kernel builds right before it on the second stream (round 6: C4 step
@@ -140,6 +141,7 @@ struct kpe_device {
   // kpe_lean6_kernel's pod-evidence table (kernels_abi.h kpe_l6_pod_table_word), built at
   // kpe_device_open: it depends on neither the policies nor a corpus
   DevBuf lean_pod_tab;
+  DevBuf lean_pod_tab_c;  // the same in the packed numbering (kpe_l6_pack_ev): launches over the compact columns
   // pinned staging for corpus uploads (two halves, double-buffered; allocated on first use): a
   // pageable hipMemcpyAsync is staged by the runtime chunk by chunk, a pinned one is one DMA
   static constexpr size_t kStageHalf = 16u << 20;
@@ -270,6 +272,10 @@ struct DeviceCorpus {
   DevBuf psum, psa_codes, psa_fixed;
   PsaCodes psa_L{};
   bool codes_ready = false;
+  // the LEAN evaluation's compact columns (kpe_lean_pack_kernel: 12-byte pod records, one word
+  // per container; kernels_abi.h), built with the codes for a corpus whose binding is LEAN6
+  DevBuf rec12, cw4;
+  bool pack_ready = false;
   Binding bind;
   bool has_masks = false;
   // rows by namespace group (kpe_fetch_namespace_counts): row ids sorted by group, the groups'
@@ -333,7 +339,7 @@ kpe_status kpe_device_open(int ordinal, kpe_device** out) {
     const int t = atoi(ev);
     d->lean_tpw = t == 1 || t == 2 || t == 4 ? (uint32_t)t : 0u;
   }
-  if (const char* ev = getenv("KPE_LEAN6_SHAPE")) d->lean_shape = (uint32_t)atoi(ev) & 3u;
+  if (const char* ev = getenv("KPE_LEAN6_SHAPE")) d->lean_shape = (uint32_t)atoi(ev) & 0x13u;
   for (int k = 0; k < d->nlanes; ++k) {
     e = hipStreamCreateWithFlags(&d->lanes[k], hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -344,10 +350,12 @@ kpe_status kpe_device_open(int ordinal, kpe_device** out) {
   }
   d->stream = d->lanes[0];
   {
-    uint32_t tab[KPE_L6_PT_WORDS];
-    for (uint32_t i = 0; i < KPE_L6_PT_WORDS; ++i) tab[i] = kpe_l6_pod_table_word(i);
+    uint32_t tab[KPE_L6_PT_WORDS], tab_c[KPE_L6_PT_WORDS];
+    for (uint32_t i = 0; i < KPE_L6_PT_WORDS; ++i) tab[i] = kpe_l6_pod_table_word(i), tab_c[i] = kpe_l6_pack_ev(tab[i]);
     e = d->lean_pod_tab.ensure(sizeof(tab));
     if (e == hipSuccess) e = hipMemcpy(d->lean_pod_tab.p, tab, sizeof(tab), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = d->lean_pod_tab_c.ensure(sizeof(tab_c));
+    if (e == hipSuccess) e = hipMemcpy(d->lean_pod_tab_c.p, tab_c, sizeof(tab_c), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
       kpe_device_close(d);
       return fail(KPE_E_DEVICE, hipGetErrorString(e));
@@ -931,6 +939,20 @@ kpe_status run_codes(const kpe::Corpus& C, kpe::DeviceCorpus& D, hipStream_t s) 
   D.codes_ready = true;
   return KPE_OK;
 }
+// The LEAN evaluation's compact columns of an uploaded corpus (kpe_lean_pack_kernel, one launch):
+// built where the codes are, for a corpus bound to kpe_lean6_kernel. Both carry 128 bytes of
+// slack; the kernel's descriptors end at n * 12 and nctr * 4 bytes (loads past those return 0).
+kpe_status run_lean_pack(const kpe::Corpus& C, kpe::DeviceCorpus& D, hipStream_t s) {
+  LeanPackArgs a{};
+  a.n = (uint32_t)C.n, a.nctr = (uint32_t)C.c_sc.size();
+  HIPCHK(D.rec12.ensure((size_t)a.n * 12 + 128));
+  HIPCHK(D.cw4.ensure((size_t)a.nctr * 4 + 128));
+  a.rec = D.rec.as<uint32_t>(), a.crec = D.crec.as<uint32_t>();
+  a.rec12 = D.rec12.as<uint32_t>(), a.cw4 = D.cw4.as<uint32_t>();
+  HIPCHK(kpe_launch_lean_pack(&a, s));
+  D.pack_ready = true;
+  return KPE_OK;
+}
 // The general scan's per-pod PSA records of an uploaded corpus on stream s (kpe_launch_psum), run
 // by every evaluation that reads them; summ: also the 2-word summaries (kpe_corpus_psa_summary),
 // or null.
@@ -953,10 +975,13 @@ kpe_status run_psum(const kpe::Corpus& C, kpe::DeviceCorpus& D, hipStream_t s, u
 }
 // Algorithmic bytes of one LEAN evaluation of a shard (kpe_lean6_kernel): the pod records, the tile
 // headers, the list columns the program reads, the code bytes and kind table its blocks stage
-// (counted once), the verdict cells and, in the masks mode, the check masks.
-double lean_bytes(const kpe::Corpus& C, const kpe::DeviceCorpus& D, uint32_t need, uint32_t R, bool masks) {
+// (counted once), the verdict cells and, in the masks mode, the check masks. compact: the launch
+// reads the 12-byte pod records and the 4-byte container words.
+double lean_bytes(const kpe::Corpus& C, const kpe::DeviceCorpus& D, uint32_t need, uint32_t R, bool masks,
+                  bool compact = false) {
   const double n = (double)C.n;
-  double b = 16.0 * n + 16.0 * (double)((C.n + 63) / 64 + 1) + 8.0 * (double)C.c_sc.size();
+  double b = (compact ? 12.0 : 16.0) * n + 16.0 * (double)((C.n + 63) / 64 + 1) +
+             (compact ? 4.0 : 8.0) * (double)C.c_sc.size();
   if (need & NEED_SANN) b += 4.0 * (double)C.c_sc.size();
   if (need & NEED_VOL) b += 4.0 * (double)C.vol_src.size();
   if (need & NEED_SYS) b += 4.0 * (double)C.sys_id.size();
@@ -1446,6 +1471,8 @@ kpe_status ensure_binding(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc
   // the PSA dictionary codes of the corpus (policy-independent; per distinct string)
   if (P.any_pss && !cc->d->codes_ready)
     if (kpe_status st = run_codes(C, *cc->d, s)) return st;
+  if (B.lean_kind == KPE_SCAN_LEAN6 && !cc->d->pack_ready)  // and the LEAN evaluation's compact columns
+    if (kpe_status st = run_lean_pack(C, *cc->d, s)) return st;
   // the general scan of a podSecurity program reads per-pod PSA records (PSUM instantiation) that
   // kpe_psum_kernel rebuilds before it every time, or (KPE_PSUM=0) walks the pods' lists
   B.gen_code = (narrow ? KPE_SCAN_NARROW : KPE_SCAN_WIDE) | (P.any_pss && !dev->no_psum ? KPE_SCAN_PSUM : 0);
@@ -1512,6 +1539,8 @@ kpe_status launch(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc, bool m
   const bool fresh = !B.inv_ready || dev->no_cache || cold;
   if (cold && P.any_pss)  // a cold evaluation rebuilds the corpus's PSA dictionary codes too
     if (kpe_status st = run_codes(C, D, s)) return st;
+  if (cold && B.lean && B.lean_kind == KPE_SCAN_LEAN6)  // and its compact columns
+    if (kpe_status st = run_lean_pack(C, D, s)) return st;
   const bool lean_go = B.lean && (!masks || B.lean_kind == KPE_SCAN_LEAN6);  // LEAN6 writes check masks too
   const bool six = lean_go && B.lean_kind == KPE_SCAN_LEAN6;
   const bool psum_go = P.any_pss && !lean_go && !dev->no_psum;  // the PSUM scan and its per-pod records
@@ -1878,6 +1907,12 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
   while (tpw > 1 && tiles / tpw < dev->lean_min_waves) tpw >>= 1;
   if (dev->lean_tpw) tpw = std::min(dev->lean_tpw, lc ? 4u : 2u);
   a.tpw = tpw;
+  // the kernel's shape: check masks, or more version classes than the evidence masks hold, take
+  // the instantiation that decides every versioned check; the others decide classes, over the
+  // compact columns unless KPE_LEAN6_SHAPE bit 4 asks for the wide records
+  const bool cv = masks || PD.ncls > KPE_L6_CLS || (dev->lean_shape & 2u);
+  bool cp = kpe_lean6_compact(lc ? 1 : 0, cv ? 1 : 0) && !(dev->lean_shape & 16u);
+  for (size_t k = 0; k < m; ++k) cp = cp && cs[k]->d->pack_ready;
   uint32_t acc = 0, kt_max = 0;
   *bytes = 0;
   for (size_t k = 0; k < m; ++k) {
@@ -1888,6 +1923,7 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
     sh.rec = D.rec.as<uint32_t>(), sh.hdr = D.hdr.as<uint32_t>(), sh.crec = D.crec.as<uint32_t>();
     sh.vol = D.vol_src.as<uint32_t>(), sh.sys = D.sys_id.as<uint32_t>(), sh.pann = D.pann_kv.as<uint32_t>();
     sh.sann = D.c_sann.as<uint32_t>();
+    sh.rec12 = D.rec12.as<uint32_t>(), sh.cw4 = D.cw4.as<uint32_t>();
     sh.codes = D.psa_codes.as<uint8_t>();
     sh.kt = B.pimg.as<uint32_t>() + B.kt_lds;
     sh.verdicts = B.verdicts.as<uint8_t>();
@@ -1900,24 +1936,22 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
     acc += (uint32_t)((C.n + 256 * tpw - 1) / (256 * tpw));  // 4 waves x tpw tiles of 64 pods per block
     kt_max = std::max(kt_max, B.nkinds);
     a.need |= B.need;
-    *bytes += lean_bytes(C, D, B.need, R, masks);
+    *bytes += lean_bytes(C, D, B.need, R, masks, cp);
   }
   a.blk0[m] = acc;
   a.kt_words = (kt_max + 3u) & ~3u;
   a.code_words = lc ? ((code_max + 15u) / 16u) * 4u : 0u;
   a.wave_words = ((KPE_L6_STAGE_BYTES + std::max(64u * R, 256u) + 15u) / 16u) * 4u;  // rows: a word per pod at least
-  // the kernel's shape: check masks, or more version classes than the evidence masks hold, take
-  // the instantiation that decides every versioned check; the others decide classes
-  const bool cv = masks || PD.ncls > KPE_L6_CLS || (dev->lean_shape & 2u);
   if (!cv)
     for (uint32_t c = 0; c < PD.ncls; ++c) {
       const KpeL6ClassMasks m = kpe_l6_class_masks(PD.cls_h[2 * c] & P.cv_union);
-      a.cls_ev[c] = m.ev, a.cls_ev_nw[c] = m.ev_nw;
+      a.cls_ev[c] = cp ? kpe_l6_pack_ev(m.ev) : m.ev, a.cls_ev_nw[c] = cp ? kpe_l6_pack_ev(m.ev_nw) : m.ev_nw;
       a.cls_rm[c] = PD.cls_h[2 * c + 1];
     }
-  a.pod_tab = dev->lean_pod_tab.as<uint32_t>();
+  a.pod_tab = (cp ? dev->lean_pod_tab_c : dev->lean_pod_tab).as<uint32_t>();
   const size_t dyn = 4 * ((size_t)KPE_L6_PT_WORDS + a.kt_words + a.code_words + 4 * (size_t)a.wave_words);
-  HIPCHK(kpe_launch_lean6(&a, dyn, lc ? 1 : 0, (a.need & NEED_SANN) || (dev->lean_shape & 1u) ? 1 : 0, cv ? 1 : 0, s));
+  HIPCHK(kpe_launch_lean6(&a, dyn, lc ? 1 : 0, (a.need & NEED_SANN) || (dev->lean_shape & 1u) ? 1 : 0, cv ? 1 : 0,
+                         cp ? 1 : 0, s));
   return KPE_OK;
 }
 

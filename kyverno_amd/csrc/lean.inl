@@ -20,6 +20,13 @@ __device__ __forceinline__ uint2 bload2(Rsrc r, uint32_t off) {
   auto v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0);
   return make_uint2(v[0], v[1]);
 }
+struct L6Rec {  // what the LEAN evaluation reads of a pod record: pod word, r_gvk, packed list counts
+  uint32_t x, y, z;
+};
+__device__ __forceinline__ L6Rec bload3(Rsrc r, uint32_t off) {
+  auto v = __builtin_amdgcn_raw_buffer_load_b96(r, off, 0, 0);
+  return L6Rec{v[0], v[1], v[2]};
+}
 __device__ __forceinline__ uint4 bload4(Rsrc r, uint32_t off) {
   auto v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
   return make_uint4(v[0], v[1], v[2], v[3]);
@@ -36,6 +43,17 @@ __device__ __forceinline__ const __attribute__((address_space(4))) void* kargs()
 #ifndef KPE_LEAN6_WAVES
 #define KPE_LEAN6_WAVES 6
 #endif
+// The verdict-only form over the compact columns (CP) holds a container in one register, not two,
+// and is compiled for eight resident blocks per CU: 64 VGPRs and, by the rule below, 80 SGPRs
+// (<4, true, false, false, true>: 60 VGPRs, no scratch, nine scalars kept in lanes). The seccomp
+// annotation form spills 13 VGPRs to scratch at eight and stays at seven.
+#ifndef KPE_LEAN6C_WAVES
+#define KPE_LEAN6C_WAVES 8
+#endif
+#ifndef KPE_LEAN6C_SANN_WAVES
+#define KPE_LEAN6C_SANN_WAVES 7
+#endif
+constexpr int l6_waves(bool sann, bool cp) { return !cp ? KPE_LEAN6_WAVES : sann ? KPE_LEAN6C_SANN_WAVES : KPE_LEAN6C_WAVES; }
 // Scalar registers of the kernel: a CU holds seven 256-thread blocks up to 96 of them and six
 // above (800 per SIMD in blocks of 16, 16 more per wave), and the compiler takes all it may.
 // The cap holds for every instantiation: the C2 one (<4, true, false, false>) fits in 94 without
@@ -214,13 +232,31 @@ __global__ void __launch_bounds__(256) kpe_psum_kernel(PsumArgs a) {
   if (a.summ) a.summ[2u * r] = xo, a.summ[2u * r + 1u] = y;
 }
 
+// ---- kpe_lean_pack_kernel: the compact columns of a corpus (once per corpus) --------------------
+// Thread i writes words {x, y, z} of pod record i and the container word of container record i
+// (kernels_abi.h kpe_l6_pack_ctr): a re-packing of the uploaded records, launched where the
+// dictionary codes are (first podSecurity binding of the corpus, and a cold evaluation).
+__global__ void __launch_bounds__(256) kpe_lean_pack_kernel(LeanPackArgs a) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < a.n) {
+    const uint4 r = reinterpret_cast<const uint4*>(a.rec)[i];
+    uint32_t* const o = a.rec12 + 3u * (size_t)i;
+    o[0] = r.x, o[1] = r.y, o[2] = r.z;
+  }
+  if (i < a.nctr) {
+    const uint2 e = reinterpret_cast<const uint2*>(a.crec)[i];
+    a.cw4[i] = kpe_l6_pack_ctr(e.x, e.y);
+  }
+}
+
 // ---- kpe_lean6_kernel: the LEAN evaluation, one or many shards per launch ----------------------
 // A wave evaluates T consecutive 64-pod tiles of its block's shard (blocks find their shard by a
 // scalar binary search over LeanBatchArgs::blk0). Two dependent memory steps per wave:
-//   1. the T + 1 tile headers (one dword per lane) and the T tiles' pod records (16 B per lane);
+//   1. the T + 1 tile headers (one dword per lane) and the T tiles' pod records (16 B per lane;
+//      CP: 12 B, one b96 load at a 12-byte stride);
 //   2. every tile's list items, cooperatively and coalesced: lane i loads container i and 64 + i
-//      of the tile (crec, and c_sann in the SANN instantiations: programs with a v1.0 seccomp
-//      check), volumes i and 64 + i, sysctl i and annotation i, from the tile's first item on.
+//      of the tile (crec, or CP: cw4; and c_sann in the SANN instantiations: programs with a v1.0
+//      seccomp check), volumes i and 64 + i, sysctl i and annotation i, from the tile's first item on.
 // Then per tile: lane i codes its staged items (capability-set / sysctl / annotation codes from
 // the corpus's code bytes, LDS-staged per block when they fit: LC) into the wave's LDS stage (a
 // container as one word: kernels_abi.h KPE_L6_*), each pod ORs its own items from there (its
@@ -233,25 +269,33 @@ __global__ void __launch_bounds__(256) kpe_psum_kernel(PsumArgs a) {
 // with the class's evidence mask (LeanBatchArgs::cls_ev), the pod word's part of that word read
 // from a constant table every block copies to LDS ahead of its kind table (kernels_abi.h
 // kpe_l6_pod_table_word). Both give the same verdicts.
+// CP (verdicts only): the pod records and containers come from the corpus's compact columns
+// (kpe_lean_pack_kernel above) and the evidence word is decided in the packed numbering
+// (kernels_abi.h KPE_L6C_*: the host passes the class masks and the pod table permuted by
+// kpe_l6_pack_ev). The slow-path loops read cw4 too. The CV forms keep the wide records.
 typedef const __attribute__((address_space(4))) LeanBatchArgs CBArgs;
 typedef const __attribute__((address_space(4))) LeanShard CShard;
-template <bool SANN>
+// CT: a loaded container, the wide record (uint2) or the compact word (uint32_t)
+template <bool SANN, class CT>
 struct L6Items;
-template <>
-struct L6Items<false> {
-  uint2 c0, c1, q0;
+template <class CT>
+struct L6Items<false, CT> {
+  CT c0, c1;
+  uint2 q0;
   uint32_t v0, v1, s0;
 };
-template <>
-struct L6Items<true> : L6Items<false> {
+template <class CT>
+struct L6Items<true, CT> : L6Items<false, CT> {
   uint32_t a0, a1;
 };
 // sysctl code (bit v: outside version v's set) at its evidence bits
 __device__ __forceinline__ uint32_t l6_sys_evidence(uint32_t c) { return ((c & 3u) << 1) | ((c & 4u) << 2); }
 
-template <int T, bool LC, bool SANN, bool CV>
-__global__ void __launch_bounds__(kLB, KPE_LEAN6_WAVES) __attribute__((amdgpu_num_sgpr(KPE_LEAN6_SGPRS)))
+template <int T, bool LC, bool SANN, bool CV, bool CP = false>
+__global__ void __launch_bounds__(kLB, l6_waves(SANN, CP)) __attribute__((amdgpu_num_sgpr(KPE_LEAN6_SGPRS)))
 kpe_lean6_kernel(LeanBatchArgs) {
+  static_assert(!(CP && CV), "the compact columns are read by the verdict-only form");
+  typedef typename std::conditional<CP, uint32_t, uint2>::type CT;
   extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
   CBArgs& a = *(CBArgs*)kargs();
   const uint32_t t = threadIdx.x, lane = t & 63u;
@@ -269,17 +313,31 @@ kpe_lean6_kernel(LeanBatchArgs) {
   const uint32_t need = a.need;
   // columns a program does not read get zero-length descriptors: their loads return 0 and move
   // no data (so do loads past a column's end)
-  const Rsrc REC = make_rsrc(S.rec, n * 16u), HDR = make_rsrc(S.hdr, (ntiles + 1u) * 16u);
-  const Rsrc CREC = make_rsrc(S.crec, S.nctr * 8u);
+  const Rsrc REC = CP ? make_rsrc(S.rec12, n * 12u) : make_rsrc(S.rec, n * 16u);
+  const Rsrc HDR = make_rsrc(S.hdr, (ntiles + 1u) * 16u);
+  const Rsrc CREC = CP ? make_rsrc(S.cw4, S.nctr * 4u) : make_rsrc(S.crec, S.nctr * 8u);
+  // container k of the column (past its end: zeros, an empty slot)
+  auto ld_ctr = [&](uint32_t k) -> CT {
+    if constexpr (CP) return bload1(CREC, k * 4u);
+    else return bload2(CREC, k * 8u);
+  };
   const Rsrc SAN = make_rsrc(S.sann, SANN && (need & NEED_SANN) ? S.nctr * 4u : 0u);
   const Rsrc VOL = make_rsrc(S.vol, (need & NEED_VOL) ? S.nvol * 4u : 0u);
   const Rsrc SYS = make_rsrc(S.sys, (need & NEED_SYS) ? S.nsys * 4u : 0u);
   const Rsrc ANN = make_rsrc(S.pann, (need & NEED_PANN) ? S.npann * 8u : 0u);
   // ---- step 1: headers (lane k: word k of hdr[tile0 + k / 4]; past the sentinel: 0), records
   const uint32_t hall = bload1(HDR, (tile0 * 4u + min(lane, 4u * T + 3u)) * 4u);
-  uint4 rec[T];
+  L6Rec rec[T];
 #pragma unroll
-  for (int j = 0; j < T; ++j) rec[j] = bload4(REC, ((tile0 + j) * 64u + lane) * 16u);  // past n: zeros
+  for (int j = 0; j < T; ++j) {  // past n: zeros
+    const uint32_t r = (tile0 + j) * 64u + lane;
+    if constexpr (CP) {
+      rec[j] = bload3(REC, r * 12u);
+    } else {
+      const uint4 w = bload4(REC, r * 16u);
+      rec[j] = L6Rec{w.x, w.y, w.z};
+    }
+  }
   // the block's kind table and (LC) code bytes, for the LDS below
   const uint32_t nk = S.nkinds;
   const uint32_t k0 = t < nk ? S.kt[t] : 0u;
@@ -295,14 +353,14 @@ kpe_lean6_kernel(LeanBatchArgs) {
     pt1 = t < KPE_L6_PT_WORDS - kLB ? gpt[t + kLB] : 0u;
   }
   // ---- step 2: the list items of every tile
-  L6Items<SANN> it[T];
+  L6Items<SANN, CT> it[T];
 #pragma unroll
   for (int j = 0; j < T; ++j) {
     if (tile0 + j >= ntiles) break;
     const uint32_t C0 = hw(hall, 4u * j), V0 = hw(hall, 4u * j + 1u), S0 = hw(hall, 4u * j + 2u),
                    A0 = hw(hall, 4u * j + 3u);
-    it[j].c0 = bload2(CREC, (C0 + lane) * 8u);
-    it[j].c1 = bload2(CREC, (C0 + 64u + lane) * 8u);
+    it[j].c0 = ld_ctr(C0 + lane);
+    it[j].c1 = ld_ctr(C0 + 64u + lane);
     if constexpr (SANN) {
       it[j].a0 = bload1(SAN, (C0 + lane) * 4u);
       it[j].a1 = bload1(SAN, (C0 + 64u + lane) * 4u);
@@ -344,14 +402,22 @@ kpe_lean6_kernel(LeanBatchArgs) {
   // item counts above which a pod takes the slow path, as scalars: a list the program does not
   // read has a limit no byte count exceeds
   const uint32_t lim_v = nvol ? 4u : 255u, lim_s = nsys ? 2u : 255u, lim_a = npann ? 2u : 255u;
-  // a container's stage word (a real record always has state bits, tested before they are masked)
-  auto ctr_word = [&](uint2 e, uint32_t cs) -> uint32_t {
-    uint32_t w = (e.x & KPE_L6_CX_USED) | ((cb(CY_CAPSET(e.y)) & 7u) << KPE_L6_CAP_SH);
-    if constexpr (SANN) w |= K.sann(cb, cs) << KPE_L6_SANN_SH;
-    return e.x ? w : 0u;
+  // a container's stage word. Wide: a real record always has state bits, tested before they are
+  // masked. Compact: a real word has KPE_L6C_REAL, which the state mask drops.
+  auto ctr_word = [&](CT e, uint32_t cs) -> uint32_t {
+    if constexpr (CP) {
+      uint32_t w = (e & ((1u << KPE_L6C_STATES) - 1u)) | ((cb(kpe_l6_ctr_capset(e)) & 7u) << KPE_L6C_CAP_SH);
+      if constexpr (SANN) w |= K.sann(cb, cs) << KPE_L6C_SANN_SH;
+      return e ? w : 0u;
+    } else {
+      uint32_t w = (e.x & KPE_L6_CX_USED) | ((cb(CY_CAPSET(e.y)) & 7u) << KPE_L6_CAP_SH);
+      if constexpr (SANN) w |= K.sann(cb, cs) << KPE_L6_SANN_SH;
+      return e.x ? w : 0u;
+    }
   };
-  // sysctl codes are staged where the pod's word wants them: cv_fails's argument, or evidence bits
-  auto sys_code = [&](uint32_t id) -> uint32_t { return CV ? K.sys(cb, id) : l6_sys_evidence(K.sys(cb, id)); };
+  // sysctl codes are staged where the pod's word wants them: cv_fails's argument (and the packed
+  // evidence word, which takes the code as it is), or in-place evidence bits
+  auto sys_code = [&](uint32_t id) -> uint32_t { return CV || CP ? K.sys(cb, id) : l6_sys_evidence(K.sys(cb, id)); };
   // the version classes' evidence masks, in scalars for every tile
   uint32_t cev[KPE_L6_CLS], cev_nw[KPE_L6_CLS], crm[KPE_L6_CLS];
 #pragma unroll
@@ -385,7 +451,7 @@ kpe_lean6_kernel(LeanBatchArgs) {
   for (int j = 0; j < T; ++j) {
     const uint32_t tile = tile0 + j;
     if (tile >= ntiles) break;
-    const L6Items<SANN>& d = it[j];
+    const L6Items<SANN, CT>& d = it[j];
     const uint32_t C0 = hw(hall, 4u * j), V0 = hw(hall, 4u * j + 1u), S0 = hw(hall, 4u * j + 2u),
                    A0 = hw(hall, 4u * j + 3u);
     const uint32_t nct = hw(hall, 4u * j + 4u) - C0, nvt = hw(hall, 4u * j + 5u) - V0,
@@ -450,7 +516,7 @@ kpe_lean6_kernel(LeanBatchArgs) {
         cw = 0;
         for (uint32_t k = oc; k < oc + nc; ++k)
           cw |= k < KPE_L6_CTR ? sc[k]
-                               : ctr_word(bload2(CREC, (C0 + k) * 8u), SANN ? bload1(SAN, (C0 + k) * 4u) : 0u);
+                               : ctr_word(ld_ctr(C0 + k), SANN ? bload1(SAN, (C0 + k) * 4u) : 0u);
       }
       if (nvol && (more_v || ov + nv > KPE_L6_VOL)) {
         vcode = 0;
@@ -484,10 +550,11 @@ kpe_lean6_kernel(LeanBatchArgs) {
         for (uint32_t c = 0; c < ncls; ++c) failr |= (fails & hw(cls_cv, c)) ? hw(cls_rm, c) : 0u;
       }
     } else {
-      const uint32_t lists = (vcode << KPE_L6_VOL_SH) | scode | (acode << KPE_L6_ANN_SH);
+      const uint32_t lists = CP ? (vcode << KPE_L6C_VOL_SH) | (scode << KPE_L6C_SYS_SH) | (acode << KPE_L6C_ANN_SH)
+                                : (vcode << KPE_L6_VOL_SH) | scode | (acode << KPE_L6_ANN_SH);
       // the pod word's part from the table: three LDS reads at constant offsets
       const uint32_t tw = kpe_l6_pod_lookup(dyn, pw);
-      const uint32_t ev = kpe_l6_pod_split(cw, tw, lists);
+      const uint32_t ev = CP ? kpe_l6c_pod_split(cw, tw, lists) : kpe_l6_pod_split(cw, tw, lists);
       const uint32_t ev_nw = ev & (uint32_t)((int32_t)tw >> 31);  // KPE_L6_PT_NW over the word
 #pragma unroll
       for (uint32_t c = 0; c < KPE_L6_CLS; ++c) {

@@ -94,58 +94,8 @@ constexpr uint32_t kBlock = 256;
 constexpr uint32_t kAllowedVolumes = PSS_ALLOWED_VOLUMES;
 
 
-// Capability-set violation bits (computed per block into LDS from the capset dictionary)
-#define CS_BASE 1u  // add has a capability outside the baseline allow-list
-#define CS_DROP 2u  // drop lacks "ALL" (also: no capabilities at all)
-#define CS_ADD 4u   // add has anything but NET_BIND_SERVICE
-
-// PSA versioned checks for one pod (PSA v0.29 policy/check_*.go, restated in
-// oracle/pss.hpp) from the pod word and the OR of its containers' state bitmaps.
-// "Containers" = initContainers + containers + ephemeralContainers.
-__device__ __forceinline__ uint32_t cv_fails(uint32_t pw, uint32_t xo, uint32_t co, bool sec_ann_bad,
-                                             bool vol_hostpath, bool vol_restricted, uint32_t sys_bad,
-                                             bool apparmor_bad, bool sec_pod_ann_bad) {
-  // Branch-free: every condition is a 0/1 value combined with & and | (no short circuit), so the
-  // whole function is selects and shifts on the lane.
-  auto on = [](uint32_t c, uint32_t cv) -> uint32_t { return (c ? 1u : 0u) << cv; };
-  const uint32_t nwin = FIELD(pw, P_OS_SH, 2) == OS_WINDOWS ? 0u : ~0u;
-  uint32_t f = 0;
-  // allowPrivilegeEscalation: some container whose APE is unset (or SC nil) or true
-  f |= (xo & (CX_APE_T | CX_APE_U)) ? (1u << CV_APE_1_8) | ((1u << CV_APE_1_25) & nwin) : 0u;
-  f |= on(apparmor_bad, CV_APPARMOR_1_0);
-  f |= on(co & CS_BASE, CV_CAPS_BASELINE_1_0);
-  f |= (co & (CS_DROP | CS_ADD)) ? (1u << CV_CAPS_RESTRICTED_1_22) | ((1u << CV_CAPS_RESTRICTED_1_25) & nwin) : 0u;
-  f |= on(pw & (P_HOSTNET | P_HOSTPID | P_HOSTIPC), CV_HOST_NS_1_0);
-  f |= on(vol_hostpath, CV_HOST_PATH_1_0);
-  f |= on(xo & CX_HOSTPORT, CV_HOST_PORTS_1_0);
-  f |= on(xo & CX_PRIV_T, CV_PRIVILEGED_1_0);
-  f |= on(xo & CX_PM_OTHER, CV_PROC_MOUNT_1_0);
-  f |= on(vol_restricted, CV_RESTRICTED_VOLUMES_1_0);
-  const uint32_t prnr = FIELD(pw, P_RNR_SH, 2);
-  f |= on((uint32_t)(prnr == TRI_FALSE) | (uint32_t)((xo & CX_RNR_F) != 0u) |
-              ((uint32_t)(prnr != TRI_TRUE) & (uint32_t)((xo & CX_RNR_U) != 0u)),
-          CV_RUN_AS_NON_ROOT_1_0);
-  f |= on((uint32_t)(FIELD(pw, P_RAU_SH, 2) == RAU_ZERO) | (uint32_t)((xo & CX_RAU_Z) != 0u), CV_RUN_AS_USER_1_23);
-  const uint32_t psel = FIELD(pw, P_SEL_SH, 3);
-  f |= on(((uint32_t)(psel != SEL_NONE) &
-           ((uint32_t)(psel == SEL_OTHER) | (uint32_t)((pw & (P_SEL_USER | P_SEL_ROLE)) != 0u))) |
-              (uint32_t)((xo & (CX_SEL_OTHER | CX_SEL_USER | CX_SEL_ROLE)) != 0u),
-          CV_SELINUX_1_0);
-  f |= on((uint32_t)sec_pod_ann_bad | (uint32_t)sec_ann_bad, CV_SECCOMP_BASELINE_1_0);
-  // pod seccomp type: valid = RuntimeDefault | Localhost, bad = set and not valid
-  const uint32_t psec = FIELD(pw, P_SECCOMP_SH, 3);
-  constexpr uint32_t kSecValid = (1u << SECCOMP_RUNTIMEDEFAULT) | (1u << SECCOMP_LOCALHOST);
-  constexpr uint32_t kSecBad = 0xFFu & ~kSecValid & ~(1u << SECCOMP_NONE);
-  const uint32_t psec_valid = (kSecValid >> psec) & 1u, psec_bad = (kSecBad >> psec) & 1u;
-  const uint32_t sec_b = psec_bad | (uint32_t)((xo & (CX_SEC_UNC | CX_SEC_OTHER)) != 0u);
-  f |= on(sec_b, CV_SECCOMP_BASELINE_1_19);
-  f |= (sec_b | ((psec_valid ^ 1u) & (uint32_t)((xo & CX_SEC_NONE) != 0u)))
-           ? (1u << CV_SECCOMP_RESTRICTED_1_19) | ((1u << CV_SECCOMP_RESTRICTED_1_25) & nwin)
-           : 0u;
-  f |= on(sys_bad & 1u, CV_SYSCTLS_1_0) | on(sys_bad & 2u, CV_SYSCTLS_1_27) | on(sys_bad & 4u, CV_SYSCTLS_1_29);
-  f |= on((uint32_t)(FIELD(pw, P_WHP_SH, 2) == TRI_TRUE) | (uint32_t)((xo & CX_WHP_T) != 0u), CV_WIN_HOST_PROCESS_1_0);
-  return f;
-}
+// CS_* (capability-set violation bits) and cv_fails (the PSA versioned checks of one pod):
+// kernels_abi.h, shared with the host checks.
 
 // The scan's arguments live in device memory (one copy per program x corpus
 // binding) and are read through the constant address space with scalar loads. The
@@ -1304,29 +1254,42 @@ extern "C" hipError_t kpe_launch_selmask(const SelMaskArgs* a, hipStream_t s) {
 // v1.0 seccomp check (reads c_sann); cv: every versioned check is decided (check masks, or more
 // than KPE_L6_CLS version classes). Without the code bytes in LDS (rare: > 8 KiB of codes) the
 // one instantiation that covers every program runs.
+// cp: the verdict-only form reads the compact columns (LeanShard::rec12 / cw4; class masks and pod
+// table in the packed numbering); kpe_lean6_compact says which launches may ask for it.
 template <int T, bool LC>
-static void lean6_go(int sann, int cv, dim3 g, dim3 b, size_t dyn_bytes, hipStream_t s, const LeanBatchArgs& a) {
+static void lean6_go(int sann, int cv, int cp, dim3 g, dim3 b, size_t dyn_bytes, hipStream_t s, const LeanBatchArgs& a) {
   if constexpr (!LC) {
     hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, true>), g, b, dyn_bytes, s, a);
   } else {
     if (sann && cv) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, true>), g, b, dyn_bytes, s, a);
+    else if (sann && cp) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, false, true>), g, b, dyn_bytes, s, a);
     else if (sann) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, false>), g, b, dyn_bytes, s, a);
     else if (cv) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, false, true>), g, b, dyn_bytes, s, a);
+    else if (cp) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, false, false, true>), g, b, dyn_bytes, s, a);
     else hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, false, false>), g, b, dyn_bytes, s, a);
   }
 }
-extern "C" hipError_t kpe_launch_lean6(const LeanBatchArgs* a, size_t dyn_bytes, int lc, int sann, int cv,
+extern "C" int kpe_lean6_compact(int lc, int cv) { return lc && !cv; }
+extern "C" hipError_t kpe_launch_lean6(const LeanBatchArgs* a, size_t dyn_bytes, int lc, int sann, int cv, int cp,
                                        hipStream_t s) {
   const uint32_t grid = a->blk0[a->nshards];
   if (a->nshards == 0 || grid == 0) return hipSuccess;
   if (!cv && a->ncls > KPE_L6_CLS) return hipErrorInvalidValue;
+  if (cp && !kpe_lean6_compact(lc, cv)) return hipErrorInvalidValue;
   const dim3 g(grid), b(kLB);
-  if (a->tpw == 4 && lc) lean6_go<4, true>(sann, cv, g, b, dyn_bytes, s, *a);
-  else if (a->tpw == 2 && lc) lean6_go<2, true>(sann, cv, g, b, dyn_bytes, s, *a);
-  else if (a->tpw == 1 && lc) lean6_go<1, true>(sann, cv, g, b, dyn_bytes, s, *a);
-  else if (a->tpw == 2) lean6_go<2, false>(sann, cv, g, b, dyn_bytes, s, *a);
-  else if (a->tpw == 1) lean6_go<1, false>(sann, cv, g, b, dyn_bytes, s, *a);
+  if (a->tpw == 4 && lc) lean6_go<4, true>(sann, cv, cp, g, b, dyn_bytes, s, *a);
+  else if (a->tpw == 2 && lc) lean6_go<2, true>(sann, cv, cp, g, b, dyn_bytes, s, *a);
+  else if (a->tpw == 1 && lc) lean6_go<1, true>(sann, cv, cp, g, b, dyn_bytes, s, *a);
+  else if (a->tpw == 2) lean6_go<2, false>(sann, cv, cp, g, b, dyn_bytes, s, *a);
+  else if (a->tpw == 1) lean6_go<1, false>(sann, cv, cp, g, b, dyn_bytes, s, *a);
   else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+// The compact columns of a corpus (lean.inl), one launch.
+extern "C" hipError_t kpe_launch_lean_pack(const LeanPackArgs* a, hipStream_t s) {
+  const uint32_t m = std::max(a->n, a->nctr);
+  if (m == 0) return hipSuccess;
+  hipLaunchKernelGGL(kpe_lean_pack_kernel, dim3((m + 255u) / 256u), dim3(256), 0, s, *a);
   return hipGetLastError();
 }
 // The PSA dictionary codes of a corpus (lean.inl), one launch.
