@@ -148,7 +148,7 @@ struct StrIndex {
   size_t n = 0;
 };
 
-struct DeviceCorpus;  // defined in kpe_api.cpp
+struct DeviceCorpus;  // defined in api_internal.h (device part)
 
 struct Corpus {
   int64_t n = 0;

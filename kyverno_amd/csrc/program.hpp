@@ -75,7 +75,7 @@ struct PssPreds {
   int32_t sysctl[3] = {-1, -1, -1};  // 1.0, 1.27, 1.29 allow-lists
 };
 
-struct DeviceProgram;  // kpe_api.cpp
+struct DeviceProgram;  // api_internal.h (device part)
 
 // What a PolicyReportResult carries for rule r besides its verdict
 // (pkg/utils/report/results.go:89-156, EngineResponseToReportResults).

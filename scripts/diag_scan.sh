@@ -8,7 +8,7 @@ set -e
 cd "$(dirname "$0")/../kyverno_amd"
 ROCM=${ROCM:-/opt/rocm}
 mkdir -p build/var
-OTHERS=$(printf 'build/%s.o ' flatten program synth pss_msg rhash kpe_api results pssx pattern pattern_trace cond cond_fepat)
+OTHERS=$(printf 'build/%s.o ' flatten program synth pss_msg rhash report kpe_api api_results results pssx pattern pattern_trace cond cond_fepat)
 for d in "$@"; do
   $ROCM/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-result -munsafe-fp-atomics -fno-vectorize \
     -fno-slp-vectorize -DKPE_DIAG=$d -c csrc/scan.hip -o build/var/scan_d$d.o

@@ -72,14 +72,18 @@ def _oracle_cv_row(oracle, pols, names, row, doc):
     return m
 
 
+def _podsecurity_message_policies():
+    return [p for p in report_policy_set()
+            if not any(((r.get("validate") or {}).get("podSecurity") or {}).get("exclude")
+                       for r in p["spec"]["rules"])]
+
+
 def test_host_messages_match_oracle(oracle):
     """kpe_report_results_msg renders podSecurity pass / fail and pattern pass messages from the
     resource JSON and the failing versioned checks; with the oracle's verdicts and checks as
     input it equals the oracle's report (oracle/pss.hpp FormatChecksPrint) on Pods and
     controllers of two synthetic mixes."""
-    pols = [p for p in report_policy_set()
-            if not any(((r.get("validate") or {}).get("podSecurity") or {}).get("exclude")
-                       for r in p["spec"]["rules"])]
+    pols = _podsecurity_message_policies()
     ps = K.PolicySet(pols)
     names = oracle.rule_names(pols)
     nmsg = 0
@@ -163,6 +167,65 @@ def test_host_deny_messages_match_oracle(oracle):
     assert any(m.startswith("pod ") for m in msgs) and any(m.startswith("labels={") for m in msgs)
     assert any(m.startswith("the produced messag") for m in msgs) and any(m.startswith("literal {{") for m in msgs)
     assert any(m.startswith("rule ") for m in msgs) and any(m.startswith("validation rule") for m in msgs)
+
+
+@pytest.fixture(scope="module")
+def report_check_bin():
+    from tests.conftest import build_host_tool
+
+    return build_host_tool("report_check")
+
+
+@pytest.mark.parametrize("which", ["podsecurity", "deny"])
+def test_renderer_under_asan_matches_the_library(oracle, report_check_bin, tmp_path, which):
+    """The renderer's source (kyverno_amd/csrc/report.cpp) built without the HIP runtime under
+    ASan / UBSan (scripts/report_check.cpp): on the policy sets and corpora of the two tests above,
+    with the oracle's verdict rows and versioned check masks, it exits 0 without a sanitizer report
+    (its bulk rendering with 1 and with 4 threads equals its per-row rendering), and its texts are
+    byte for byte libkpe.so's for the same inputs."""
+    import ctypes
+    import subprocess
+
+    from kyverno_amd._lib import load
+
+    pols, mixes = {"podsecurity": (_podsecurity_message_policies(), ((0, 0xC2), (2, 31))),
+                   "deny": (_deny_message_policies(), ((2, 0x3D), (4, 5)))}[which]
+    ps = K.PolicySet(pols)
+    names = oracle.rule_names(pols)
+    lines = []
+    for mix, seed in mixes:  # every 12th row of each corpus: 50 rows
+        lines += [x for x in K.synth_resources(seed, 300, mix=mix).split(b"\n") if x.strip()][::12]
+    nd = b"\n".join(lines) + b"\n"
+    v = np.ascontiguousarray(oracle.validate(pols, nd, nthreads=4), dtype=np.uint8)
+    m = np.stack([_oracle_cv_row(oracle, pols, names, v[i], json.loads(x)) for i, x in enumerate(lines)])
+    assert v.shape == m.shape == (len(lines), ps.num_rules) and m.dtype == np.uint32
+    (tmp_path / "policies.json").write_bytes(json.dumps(pols).encode())
+    (tmp_path / "resources.ndjson").write_bytes(nd)
+    (tmp_path / "rows.bin").write_bytes(np.array(v.shape, dtype=np.uint64).tobytes() + v.tobytes() + m.tobytes())
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1")
+    res = subprocess.run([report_check_bin] + [str(tmp_path / f) for f in
+                                               ("policies.json", "resources.ndjson", "rows.bin", "texts.bin")],
+                         env=env, capture_output=True, text=True)
+    assert res.returncode == 0, (res.stdout, res.stderr)
+    assert "Sanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr
+    raw = (tmp_path / "texts.bin").read_bytes()
+    n = int(np.frombuffer(raw, np.uint64, 1)[0])
+    assert n == len(lines)
+    off = np.frombuffer(raw, np.uint64, n + 1, 8).astype(np.int64)
+    texts = raw[8 * (n + 2):]
+    assert off[n] == len(texts)
+    L, corpus = load(), K.Corpus(nd)
+    nmsg = 0
+    for i, x in enumerate(lines):
+        cap = 1 << 16
+        buf = ctypes.create_string_buffer(cap)
+        k = L.kpe_report_results_msg_tr(ps.h, corpus.h, v[i].ctypes.data, m[i].ctypes.data, None, x, len(x), buf, cap)
+        assert 0 <= k < cap
+        got = texts[off[i]:off[i + 1]]
+        assert got == buf.raw[:k], (i, got, buf.raw[:k])
+        assert json.loads(got) == K.report_results(ps, v[i], m[i], resource=x)
+        nmsg += got.count(b'"message"')
+    assert nmsg > 50
 
 
 def test_host_report_matches_oracle_without_controls(oracle):
