@@ -81,7 +81,14 @@ void kpe_device_close(kpe_device* dev);
 /* policies_json: one ClusterPolicy/Policy object or a JSON array of them
  * (kyverno.io/v1 schema, api/kyverno/v1/spec_types.go:240-284). Autogen is
  * applied (autogen.ComputeRules). Rules are laid out policy-major, in
- * ComputeRules order: column r of the verdict matrix is rule r. */
+ * ComputeRules order: column r of the verdict matrix is rule r.
+ * The JMESPath of {{ }} variables and foreach lists includes filter steps `<chain>[?P]` over a
+ * single value (P: comparators, `!`, `&&`, `||`, parentheses over element-relative chains, `@` and
+ * scalar literals, and contains / starts_with / ends_with with contains(keys(x), 'name')), followed
+ * by the steps that may follow `[*]`; a filter's own element list is a result only as a foreach
+ * list. Anything outside the device subset is KPE_E_UNSUPPORTED. A filter
+ * that keeps more than 32 elements, or compares two arrays / two objects, leaves the cell
+ * KPE_UNDECIDED. */
 kpe_status kpe_program_compile(const char* policies_json, size_t len, kpe_program** out);
 /* kpe_program_compile with PolicyExceptions (kyverno.io/v2beta1, api/kyverno/v2beta1/
  * policy_exception_types.go; the exception lister of engine.NewEngine, pkg/engine/exceptions.go:12-35,

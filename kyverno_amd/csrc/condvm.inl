@@ -9,6 +9,7 @@
 //   engine.go:278-285 (preconditions), validate_resource.go:186-279 (foreach, deny),
 //   utils/foreach.go:12-63 (EvaluateList, AddElementToContext)
 //   go-jmespath (go.mod:33) field / index / flatten / projection / multi-select / keys / `||`,
+//   filter projections `[?P]` (comparators, `!`, `&&`, `||` and calls in P as branch code: leaf()),
 //   functions.go length / keys / values / contains / starts_with / ends_with / not_null
 // Every function is forced inline and each heavy one has a single call site (cond_eval_row is a
 // state machine around one block() call): a call would receive the lane's private list buffers
@@ -19,6 +20,12 @@
 
 #ifndef CV_LIST_CAP
 #define CV_LIST_CAP 32
+#endif
+// Filter steps `[?P]` (QO_FILT, leaf()) are compiled only into the build of the VM that runs the
+// programs holding one (cond_filt.hip): the instances that run every other program keep the
+// registers and the instruction stream they have without them.
+#ifndef KPE_COND_FILT
+#define KPE_COND_FILT 0
 #endif
 constexpr int kCvBufs = 6 + KPE_FE_DEPTH;  // key: 0,1 (+2 list template); value: 3,4 (+5); foreach
                                            // lists: 6 + nesting level
@@ -236,6 +243,80 @@ struct CondVM {
     return CS_OK;
   }
 
+#if KPE_COND_FILT
+  // x == y for two values of the same scalar type t (deep_equal, oracle/conditions.hpp:99-105)
+  __device__ __forceinline__ bool scalar_eq(CV x, CV y, uint32_t t) const {
+    return t == JT_NULL || (t == JT_BOOL && btrue(x) == btrue(y)) || (t == JT_NUM && num(x) == num(y)) ||
+           (t == JT_STR && seq(str(x), str(y)));
+  }
+  // One leaf of a filter predicate (schema.h QO_LEAF at ops[at - 1], its operand ops from `at`) on
+  // element k of src (fetched again where an operand starts, so that it is not live across the
+  // walk): 1 truthy, 0 false-like, -1 undecided, -2 an invalid-type error. Restates
+  // oracle/conditions.hpp Interp::eval N_CMP :675-686 (deep_equal :99-128: type-strict, numbers
+  // as float64; an ordering comparator is null, so false-like, unless both sides are numbers),
+  // is_false :89-98 and Interp::call :692-738 (keys :698-704, contains :717-730, starts_with /
+  // ends_with :731-738). Operand chains are never strict (N_FIELD :598-604 with strict unset:
+  // a query with a filter is no plain chain, :789-799). Both operands are walked by one loop, so
+  // field() / index() are inlined once; no value leaves the registers. A comparison of two
+  // arrays or two objects (a deep comparison) is undecided.
+  __device__ __forceinline__ int leaf(CV src, uint32_t k, uint32_t hx, uint32_t at) {
+    const uint32_t kind = FL_KIND(hx), na = FL_NA(hx);
+    const uint32_t tot = na + (kind == FL_HASKEY ? 0u : FL_NB(hx));
+    CV x = aget(src, k), A = x;
+    for (uint32_t j = 0;; ++j) {
+      if (j == na) A = x, x = aget(src, k);
+      if (j >= tot) break;
+      const uint2 q = a.ops[at + j];
+      const uint32_t qo = QO_OP(q.x);
+      int st = CS_OK;
+      if (qo == QO_CONST) x = SC_TYPE(a.ctab[q.y].flags) == SC_T_NULL ? cv(VK_NULL, 0) : cv(VK_CONST, q.y);
+      else x = qo == QO_FIELD ? field(x, q.y, false, &st) : index(x, (int32_t)q.y);
+    }
+    const CV B = x;
+    const uint32_t ta = type(A), tb = type(B);
+    switch (kind) {
+      case FL_TRUTHY: return !is_false(A);
+      case FL_EQ:
+      case FL_NE: {
+        if (ta != tb) return kind == FL_NE;
+        if (ta == JT_ARR || ta == JT_OBJ) return -1;
+        return scalar_eq(A, B, ta) != (kind == FL_NE);
+      }
+      case FL_LT:
+      case FL_LE:
+      case FL_GT:
+      case FL_GE: {
+        if (ta != JT_NUM || tb != JT_NUM) return 0;
+        const double p = num(A), q = num(B);
+        return kind == FL_LT ? p < q : kind == FL_LE ? p <= q : kind == FL_GT ? p > q : p >= q;
+      }
+      case FL_HASKEY:  // contains(keys(A), '<name>'): a member test (a null member is present)
+        if (ta != JT_OBJ) return -2;
+        return lookup(A.p, a.fkeys[a.ops[at + na].y]) != kNoNode;
+      default: break;
+    }
+    bool h = false;
+    if (kind == FL_CONTAINS && ta == JT_ARR) {  // some element deep-equals the needle
+      const uint32_t n = alen(A);
+      for (uint32_t m = 0; m < n && !h; ++m) {
+        const CV e = aget(A, m);
+        if (type(e) != tb) continue;
+        if (tb == JT_ARR || tb == JT_OBJ) return -1;
+        h = scalar_eq(e, B, tb);
+      }
+      return h;
+    }
+    if (ta != JT_STR || tb != JT_STR) return -2;
+    const SView s = str(A), p = str(B);
+    if (p.n <= s.n) {
+      int o = kind == FL_ENDS ? s.n - p.n : 0;
+      const int oe = kind == FL_CONTAINS ? s.n - p.n : o;
+      for (; o <= oe && !h; ++o) h = bytes_eq(s.s + o, p.s, p.n);
+    }
+    return h;
+  }
+#endif  // KPE_COND_FILT
+
   // One expression (no `||`): the result may be a list in buffer b0 or b1.
   __device__ __forceinline__ int run_ops(const KpeCExpr& e, uint32_t b0, uint32_t b1, CV* out) {
     const bool strict = e.flags & CE_STRICT;
@@ -257,6 +338,9 @@ struct CondVM {
         if (op == QO_MSL) {
           for (uint32_t k = 0; k < QO_ARG(o.x); ++k) i += 1u + QO_ARG(a.ops[i].x);
         }
+#if KPE_COND_FILT
+        if (op == QO_FILT) i += QO_ARG(o.x);  // its predicate
+#endif
         continue;
       }
       switch (op) {
@@ -379,6 +463,34 @@ struct CondVM {
           cur = cv(VK_LIST, fb);
           break;
         }
+#if KPE_COND_FILT
+        case QO_FILT: {  // N_FILTER (oracle/conditions.hpp:643-653): the left side not an array is
+          // null; an element is kept unless P is false-like, tested before it is pushed, so that
+          // CV_LIST_CAP bounds the survivors. P is branch code (N_AND :669-672, N_OR :660-668 and
+          // N_NOT :673 are its targets): the op cursor is all its state, and a leaf is evaluated
+          // exactly when the interpreter's short circuit evaluates it.
+          const uint32_t p0 = i;
+          i += QO_ARG(o.x);
+          if (type(cur) != JT_ARR) {
+            mode = 2;
+            break;
+          }
+          const uint32_t fb = free_buf();
+          blen[fb] = 0;
+          for (uint32_t k = 0; k < alen(cur); ++k) {
+            uint32_t pc = 0;
+            while (pc < FL_DROP) {  // the op cursor is the predicate's whole state
+              const int t = leaf(cur, k, a.ops[p0 + pc].x, p0 + pc + 1u);
+              if (t < 0) return t == -1 ? CS_UNDEC : CS_ERROR;
+              const uint32_t to = a.ops[p0 + pc].y;
+              pc = t ? FL_T(to) : FL_F(to);
+            }
+            if (pc == FL_KEEP && push(fb, aget(cur, k))) return CS_UNDEC;
+          }
+          lb = fb, mode = 1;
+          break;
+        }
+#endif
         case QO_LEN: {  // jpfLength (go-jmespath functions.go): runes / items / members
           uint32_t len = 0;
           if (mode == 1) {
@@ -401,7 +513,7 @@ struct CondVM {
           cur = cv(VK_NUM, len);
           break;
         }
-        default: return CS_ERROR;  // QO_ERROR: an empty expression
+        default: return CS_ERROR;  // QO_ERROR: an empty expression (QO_FILT in a build without filters)
       }
     }
     if (mode == 2) {

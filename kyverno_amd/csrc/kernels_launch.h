@@ -40,8 +40,10 @@ hipError_t kpe_launch_leaf_table(const PatArgs* dargs, const uint32_t* slot_leaf
 hipError_t kpe_launch_pattern(const PatArgs* dargs, int64_t n, uint32_t npr, int lt, hipStream_t s);
 hipError_t kpe_launch_pattern_trace(const PatArgs* dargs, const uint64_t* cells, uint64_t n, uint32_t* out,
                                     const uint4* jobs, hipStream_t s);
-// cond.hip, cond_fepat.hip (kpe_launch_cond forwards to the FEPAT instance's launcher)
-hipError_t kpe_launch_cond(const CondArgs* dargs, int64_t n, int fepat, int txt, hipStream_t s);
+// cond.hip, cond_fepat.hip, cond_filt.hip (kpe_launch_cond forwards to the other two launchers)
+// (filt: the program holds a filter step `[?P]`: cond_filt.hip's build of the kernel)
+hipError_t kpe_launch_cond(const CondArgs* dargs, int64_t n, int fepat, int filt, int txt, hipStream_t s);
+hipError_t kpe_launch_cond_filt(const CondArgs* dargs, int64_t n, int txt, hipStream_t s);
 hipError_t kpe_launch_cond_fepat(const CondArgs* dargs, int64_t n, int txt, hipStream_t s);
 // pssx.hip
 hipError_t kpe_launch_pssx(const PssxArgs* dargs, int64_t n, hipStream_t s);

@@ -1289,7 +1289,8 @@ kpe_status launch(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc, bool m
       HIPCHK(hipStreamSynchronize(s));
       B.cargs_valid = true;
     }
-    HIPCHK(kpe_launch_cond(B.cargs.as<CondArgs>(), C.n, P.any_fe_pat ? 1 : 0, P.cond.tpieces.empty() ? 0 : 1, s));
+    HIPCHK(kpe_launch_cond(B.cargs.as<CondArgs>(), C.n, P.any_fe_pat ? 1 : 0, P.cond.any_filter ? 1 : 0,
+                           P.cond.tpieces.empty() ? 0 : 1, s));
   }
   if (!P.pssx.rules.empty()) {
     if (!B.xargs_valid || (masks ? B.masks.p : nullptr) != B.xmasks) {

@@ -1204,14 +1204,18 @@ CondMsgs cond_msgs(const JV* j) {
 //     an invalid-type error), keys(<chain>) / values(<chain>) in function form, and the calls
 //     contains / starts_with / ends_with / not_null as the whole query or an operand of its
 //     top-level `||` (arguments: `||` chains of the chains above, no other call; arity checked
-//     here). Parse errors of an empty expression are run-time errors; anything outside the subset
-//     is refused;
+//     here), and a filter `<chain>[?P]` over a single value, then projected like `[*]`
+//     (QueryParser::predicate: P is comparators, `!`, `&&`, `||`, parentheses and contains /
+//     starts_with / ends_with over element-relative chains, `@` and scalar literals; the filter's
+//     own element list is a result only as a foreach list, and `[*]` after a filter is refused).
+//     Parse errors of an empty expression are run-time errors; anything outside the subset is
+//     refused;
 //   * operators Equals / NotEquals / AnyIn / AllIn / AnyNotIn / AllNotIn / In / NotIn
 //     (variables/operator/*.go); InRange values of set operators are refused (as the oracle).
 namespace cq {
 
 enum Tok { T_EOF, T_ID, T_QID, T_NUM, T_DOT, T_STAR, T_FLAT, T_LBRACK, T_RBRACK, T_COMMA, T_LPAREN, T_RPAREN,
-           T_CUR, T_OR, T_LIT, T_RAW, T_PIPE, T_OTHER };
+           T_CUR, T_OR, T_LIT, T_RAW, T_PIPE, T_FILTER, T_AND, T_NOT, T_EQ, T_NE, T_LT, T_LE, T_GT, T_GE, T_OTHER };
 struct Token {
   Tok t;
   std::string s;
@@ -1307,11 +1311,29 @@ std::vector<Token> lex(const std::string& q) {
       i += 2;
       continue;
     }
+    // `[?`, `&&`, `!` and the comparators: accepted inside a filter predicate only (QueryParser)
+    static const struct {
+      char a, b;
+      Tok t;
+    } kTwo[] = {{'[', '?', T_FILTER}, {'&', '&', T_AND}, {'=', '=', T_EQ}, {'!', '=', T_NE}, {'<', '=', T_LE},
+                {'>', '=', T_GE}};
+    bool hit = false;
+    for (auto& w : kTwo)
+      if (two(w.a, w.b)) {
+        out.push_back({w.t});
+        i += 2;
+        hit = true;
+        break;
+      }
+    if (hit) continue;
     Tok t = T_OTHER;
     switch (c) {
       case '.': t = T_DOT; break;
       case '*': t = T_STAR; break;
-      case '[': t = (i + 1 < q.size() && q[i + 1] == '?') ? T_OTHER : T_LBRACK; break;
+      case '[': t = T_LBRACK; break;
+      case '!': t = T_NOT; break;
+      case '<': t = T_LT; break;
+      case '>': t = T_GT; break;
       case ']': t = T_RBRACK; break;
       case ',': t = T_COMMA; break;
       case '(': t = T_LPAREN; break;
@@ -1442,7 +1464,9 @@ class QueryParser {
   QueryParser(CondProgram& cp, Consts& k) : CP(cp), K(k) {}
 
   // a whole query (a {{ }} variable text or a foreach list); returns the expression index
-  uint32_t compile(const std::string& q0) {
+  // (list: a foreach list, the one place where a filter's own element list may be the result)
+  uint32_t compile(const std::string& q0, bool list = false) {
+    as_list_ = list;
     std::string q = q0;
     while (!q.empty() && isspace((unsigned char)q.back())) q.pop_back();
     size_t b = 0;
@@ -1457,18 +1481,31 @@ class QueryParser {
     t_ = lex(q);
     i_ = 0;
     in_call_ = false;
-    if (std::any_of(t_.begin(), t_.end(), [](const Token& t) { return t.t == T_PIPE; })) {
+    // tokens outside every filter predicate (a predicate's own `||` is no operand of the query)
+    auto outside = [&](Tok want) {
+      int depth = 0, in = 0;  // bracket depth; the depth at which the open filter started
+      for (const Token& t : t_) {
+        if (t.t == T_FILTER && !in) in = depth + 1;
+        if (t.t == T_FILTER || t.t == T_LBRACK) ++depth;
+        if (t.t == T_RBRACK) {
+          if (in == depth) in = 0;
+          --depth;
+        }
+        if (!in && t.t == want) return true;
+      }
+      return false;
+    };
+    if (outside(T_PIPE)) {
       // `<chain> | length(@)`, the one pipe on the device: the pipe binds loosest (a `||` would
       // sit inside one of its sides), so no `||` is accepted with it
-      if (std::any_of(t_.begin(), t_.end(), [](const Token& t) { return t.t == T_OR; }))
-        throw CompileError("JMESPath pipe with `||` is not supported on the device: " + q);
+      if (outside(T_OR)) throw CompileError("JMESPath pipe with `||` is not supported on the device: " + q);
       bool pl = true;
       std::vector<uint32_t> c = chain(&pl);
       if (!(cur().t == T_PIPE && peek().t == T_ID && peek().s == "length" && peek(2).t == T_LPAREN &&
             peek(3).t == T_CUR && peek(4).t == T_RPAREN && peek(5).t == T_EOF))
         throw CompileError("JMESPath pipe other than `| length(@)` is not supported on the device: " + q);
       op(c, QO_LEN);
-      KpeCExpr e{(uint32_t)CP.ops.size() / 2, (uint32_t)c.size() / 2, 0, CE_NONE};  // a pipe: not strict
+      KpeCExpr e{(uint32_t)CP.ops.size() / 2, (uint32_t)c.size() / 2, has_filter(c) ? CE_BUFS : 0u, CE_NONE};  // a pipe: not strict
       CP.ops.insert(CP.ops.end(), c.begin(), c.end());
       CP.exprs.push_back(e);
       return (uint32_t)CP.exprs.size() - 1;
@@ -1485,6 +1522,13 @@ class QueryParser {
   size_t i_ = 0;
   bool in_call_ = false;     // inside a call's argument list
   bool last_proj_ = false;   // the chain just parsed ended inside a projection
+  bool ends_filter_ = false;  // ... and its last step was a filter `[?P]`
+  bool as_list_ = false;      // the query is a foreach list
+  static bool has_filter(const std::vector<uint32_t>& o) {
+    for (size_t k = 0; k < o.size(); k += 2)
+      if (QO_OP(o[k]) == QO_FILT) return true;
+    return false;
+  }
   uint32_t ctrue_ = CE_NONE;  // the interned JSON `true` (the next constant is `false`)
   struct Operand {
     std::vector<uint32_t> ops;
@@ -1504,9 +1548,14 @@ class QueryParser {
         x.plain = false;
       } else {
         x.ops = chain(&x.plain);
+        // The filter's own element list (maps, which no operator compares) is a result only as a
+        // foreach list
+        if (ends_filter_ && !(top && as_list_))
+          throw CompileError("a JMESPath filter's element list as a value is not supported on the device");
         for (size_t k = 0; k < x.ops.size(); k += 2) {
           const uint32_t o = QO_OP(x.ops[k]);
-          if (o == QO_FLAT || o == QO_STAR || o == QO_KEYS || o == QO_VALS || o == QO_FVALS || o == QO_MSL)
+          if (o == QO_FLAT || o == QO_STAR || o == QO_KEYS || o == QO_VALS || o == QO_FVALS || o == QO_MSL ||
+              o == QO_FILT)
             x.flags |= CE_BUFS;
         }
       }
@@ -1596,9 +1645,194 @@ class QueryParser {
       }
     }
   }
+  // ---- filter predicates ---------------------------------------------------------------------
+  // `[?P]`, the `[?` consumed: P parsed with go-jmespath's binding powers (parser.go; `!` 45 binds
+  // tighter than the comparators 5, then `&&` 3, then `||` 2) and compiled to branch code over its
+  // leaves (schema.h QO_LEAF): only P's truthiness is needed, so every leaf carries where to go on
+  // when it is truthy and when it is false-like, and `!` swaps the two. A comparator whose
+  // operand would be a `!`, `&&`, `||` or parenthesised expression, or a call, is refused.
+  struct PNode {
+    int t = 0;  // 0 leaf, 1 `!`, 2 `&&`, 3 `||`
+    std::shared_ptr<PNode> l, r;
+    uint32_t kind = FL_TRUTHY;
+    std::vector<uint32_t> a, b;
+    bool ate_not = false;  // a leaf that already stands for `!<operand>.<steps>` (p_leaf)
+  };
+  using PPtr = std::shared_ptr<PNode>;
+  static bool cmp_tok(Tok t) { return t == T_EQ || t == T_NE || t == T_LT || t == T_LE || t == T_GT || t == T_GE; }
+  // an operand: a scalar literal, `@`, or a chain of fields / indexes relative to the element
+  // (tight: the operand of a `!`, which binds tighter (45) than `.` (40) but not than `[N]` (55))
+  std::vector<uint32_t> p_operand(bool tight = false) {
+    std::vector<uint32_t> o;
+    if (cur().t == T_RAW || cur().t == T_LIT) {
+      const JV& v = cur().lit;
+      if (v.t == JV::Arr || v.t == JV::Obj)
+        throw CompileError("array / object literals in a filter predicate are not supported on the device");
+      op(o, QO_CONST, K.scalar(v));
+      ++i_;
+      return o;
+    }
+    if (cur().t == T_CUR) {
+      ++i_;
+    } else if (name_tok() && peek().t != T_LPAREN) {
+      op(o, QO_FIELD, field(cur().s));
+      ++i_;
+    } else {
+      throw CompileError("filter predicate operand outside the device subset");
+    }
+    for (;;) {
+      if (!tight && cur().t == T_DOT && (peek().t == T_ID || peek().t == T_QID) && peek(2).t != T_LPAREN) {
+        op(o, QO_FIELD, field(peek().s));
+        i_ += 2;
+      } else if (cur().t == T_LBRACK && peek().t == T_NUM && peek(2).t == T_RBRACK) {
+        op(o, QO_INDEX, (uint32_t)(int32_t)peek().n);
+        i_ += 3;
+      } else {
+        break;
+      }
+    }
+    if (o.size() / 2 > 255) throw CompileError("filter predicate operand too long for the device");
+    return o;
+  }
+  PPtr p_leaf(bool allow_cmp) {
+    auto n = std::make_shared<PNode>();
+    if (cur().t == T_ID && peek().t == T_LPAREN) {  // contains / starts_with / ends_with
+      const std::string fn = cur().s;
+      if (fn != "contains" && fn != "starts_with" && fn != "ends_with")
+        throw CompileError("JMESPath function " + fn + "() in a filter predicate is not supported on the device");
+      n->kind = fn == "contains" ? FL_CONTAINS : fn == "starts_with" ? FL_STARTS : FL_ENDS;
+      i_ += 2;
+      bool keys = false;
+      if (fn == "contains" && cur().t == T_ID && cur().s == "keys" && peek().t == T_LPAREN) {
+        i_ += 2;
+        keys = true;
+      }
+      n->a = p_operand();
+      if (keys) {
+        if (n->a.size() && QO_OP(n->a[0]) == QO_CONST) throw CompileError("keys() of a literal");
+        if (cur().t != T_RPAREN) throw CompileError("keys() argument in a filter predicate outside the device subset");
+        ++i_;
+      }
+      if (cur().t != T_COMMA) throw CompileError("JMESPath: invalid arity for " + fn + "()");
+      ++i_;
+      if (keys) {  // a member test against the bound field-key table
+        if (!((cur().t == T_RAW || cur().t == T_LIT) && cur().lit.t == JV::Str))
+          throw CompileError("contains(keys(...), x): x other than a string literal is not supported on the device");
+        n->kind = FL_HASKEY;
+        op(n->b, QO_FIELD, field(cur().lit.s));
+        ++i_;
+      } else {
+        n->b = p_operand();
+      }
+      if (cur().t != T_RPAREN) throw CompileError("JMESPath: invalid arity for " + fn + "()");
+      ++i_;
+      return n;
+    }
+    n->a = p_operand(!allow_cmp);
+    if (!allow_cmp && cur().t == T_DOT && (peek().t == T_ID || peek().t == T_QID) && peek(2).t != T_LPAREN) {
+      // `!a.b` is `(!a).b` (oracle/conditions.hpp Parser::bp: T_NOT 45 above T_DOT 40): a member
+      // of a boolean, so null whatever the element holds; the steps after it keep it null
+      for (;;) {
+        if (cur().t == T_DOT && (peek().t == T_ID || peek().t == T_QID) && peek(2).t != T_LPAREN) i_ += 2;
+        else if (cur().t == T_LBRACK && peek().t == T_NUM && peek(2).t == T_RBRACK) i_ += 3;
+        else break;
+      }
+      n->a.clear();
+      op(n->a, QO_CONST, K.scalar(JV()));
+      n->ate_not = true;
+      return n;
+    }
+    if (allow_cmp && cmp_tok(cur().t)) {
+      const Tok c = cur().t;
+      n->kind = c == T_EQ ? FL_EQ : c == T_NE ? FL_NE : c == T_LT ? FL_LT : c == T_LE ? FL_LE : c == T_GT ? FL_GT : FL_GE;
+      ++i_;
+      n->b = p_operand();
+    }
+    return n;
+  }
+  PPtr p_not(bool allow_cmp) {
+    PPtr n;
+    if (cur().t == T_NOT) {
+      ++i_;
+      n = std::make_shared<PNode>();
+      n->t = 1, n->l = p_not(false);  // `!a == b` compares `!a`
+      // `!!a.b` is `(!!a).b`: every `!` in front of the dotted operand belongs to its first name
+      if (n->l->t == 0 && n->l->ate_not) n = n->l;
+    } else if (cur().t == T_LPAREN) {
+      ++i_;
+      n = p_or();
+      if (cur().t != T_RPAREN) throw CompileError("filter predicate outside the device subset");
+      ++i_;
+      n->ate_not = false;  // `!(!a.b)` negates the parenthesised value
+    } else {
+      n = p_leaf(allow_cmp);
+    }
+    if (cmp_tok(cur().t))
+      throw CompileError("a comparison of `!`, `&&`, `||`, parenthesised or call results is not supported on the device");
+    return n;
+  }
+  PPtr p_and() {
+    PPtr l = p_not(true);
+    while (cur().t == T_AND) {
+      ++i_;
+      auto n = std::make_shared<PNode>();
+      n->t = 2, n->l = l, n->r = p_not(true);
+      l = n;
+    }
+    return l;
+  }
+  PPtr p_or() {
+    PPtr l = p_and();
+    while (cur().t == T_OR) {
+      ++i_;
+      auto n = std::make_shared<PNode>();
+      n->t = 3, n->l = l, n->r = p_and();
+      l = n;
+    }
+    return l;
+  }
+  static uint32_t p_count(const PNode& n) { return n.t == 0 ? 1u : p_count(*n.l) + (n.r ? p_count(*n.r) : 0u); }
+  struct PLeaf {
+    const PNode* n;
+    int t, f;  // a leaf index, -1 keep, -2 drop
+  };
+  static void p_gen(const PNode& n, uint32_t base, int t, int f, std::vector<PLeaf>& out) {
+    if (n.t == 0) {
+      out[base] = PLeaf{&n, t, f};
+    } else if (n.t == 1) {
+      p_gen(*n.l, base, f, t, out);
+    } else {
+      const int r = (int)(base + p_count(*n.l));
+      if (n.t == 2) p_gen(*n.l, base, r, f, out);
+      else p_gen(*n.l, base, t, r, out);
+      p_gen(*n.r, (uint32_t)r, t, f, out);
+    }
+  }
+  std::vector<uint32_t> predicate() {
+    const PPtr root = p_or();
+    if (cur().t != T_RBRACK) throw CompileError("filter predicate outside the device subset");
+    ++i_;
+    const uint32_t nl = p_count(*root);
+    if (nl > KPE_FILT_LEAVES) throw CompileError("filter predicate with more leaves than the device encoding holds");
+    std::vector<PLeaf> lv(nl);
+    p_gen(*root, 0, -1, -2, lv);
+    std::vector<uint32_t> off(nl);
+    uint32_t at = 0;
+    for (uint32_t k = 0; k < nl; ++k) off[k] = at, at += 1u + (uint32_t)(lv[k].n->a.size() + lv[k].n->b.size()) / 2;
+    auto target = [&](int l) { return l == -1 ? FL_KEEP : l == -2 ? FL_DROP : off[(size_t)l]; };
+    std::vector<uint32_t> o;
+    for (const PLeaf& L : lv) {
+      op(o, QO_LEAF | L.n->kind << 8 | (uint32_t)(L.n->a.size() / 2) << 16 | (uint32_t)(L.n->b.size() / 2) << 24,
+         target(L.t) | target(L.f) << 16);
+      o.insert(o.end(), L.n->a.begin(), L.n->a.end());
+      o.insert(o.end(), L.n->b.begin(), L.n->b.end());
+    }
+    return o;
+  }
+
   std::vector<uint32_t> chain(bool* plain) {
     std::vector<uint32_t> o;
-    last_proj_ = false;
+    last_proj_ = false, ends_filter_ = false;
     // ---- root ----
     if (cur().t == T_RAW || cur().t == T_LIT) {
       op(o, QO_CONST, K.value(cur().lit));
@@ -1631,6 +1865,7 @@ class QueryParser {
       ++i_;
       op(o, QO_LEN);
       *plain = false;
+      last_proj_ = false, ends_filter_ = false;  // a number
       return o;
     }
     if (r == "request") {
@@ -1653,9 +1888,27 @@ class QueryParser {
     // ---- steps ----
     bool proj = false;  // inside a projection (steps apply per element)
     bool keys_open = false;
+    bool filt = false;  // the last step was a filter
+    bool filtered = false;  // a filter has been seen
     for (;;) {
       const Token& t = cur();
       if (keys_open && t.t != T_FLAT) throw CompileError("keys(@) inside a projection must be flattened");
+      if (t.t == T_FILTER) {
+        // `[?P]` over a single value; then `.field`, `[N]` and `[]` apply per surviving element
+        // (`[*]` after it would project each survivor: refused below). Inside a projection it would
+        // give a list per element, and in a call's argument the list buffers may hold argument 0
+        if (proj) throw CompileError("a JMESPath filter inside a projection is not supported on the device");
+        if (in_call_) throw CompileError("a JMESPath filter inside a call's argument is not supported on the device");
+        ++i_;
+        const std::vector<uint32_t> p = predicate();
+        op(o, QO_FILT | (uint32_t)(p.size() / 2) << 8);
+        CP.any_filter = true;
+        o.insert(o.end(), p.begin(), p.end());
+        *plain = false;
+        proj = true, filt = true, filtered = true;
+        continue;
+      }
+      if (t.t == T_DOT || t.t == T_LBRACK || t.t == T_FLAT) filt = false;
       if (t.t == T_DOT && (peek().t == T_ID || peek().t == T_QID)) {
         if (peek().t == T_ID && peek().s == "keys" && peek(2).t == T_LPAREN) {
           if (peek(3).t != T_CUR || peek(4).t != T_RPAREN) throw CompileError("keys() argument other than @");
@@ -1684,6 +1937,7 @@ class QueryParser {
         proj = true;
         i_ += 2;
       } else if (t.t == T_LBRACK && peek().t == T_STAR && peek(2).t == T_RBRACK) {
+        if (filtered) throw CompileError("`[*]` after a JMESPath filter is not supported on the device");
         op(o, QO_STAR);
         *plain = false;
         proj = true;
@@ -1710,7 +1964,7 @@ class QueryParser {
       }
     }
     if (keys_open) throw CompileError("keys(@) inside a projection must be flattened");
-    last_proj_ = proj;
+    last_proj_ = proj, ends_filter_ = filt;
     return o;
   }
 };
@@ -1898,7 +2152,7 @@ class CondCompiler {
   // a foreach list: a query template (the device evaluates it through the condition-value path)
   uint32_t list_query(const std::string& q) {
     KpeVTmpl t{};
-    t.kind = VT_QUERY, t.a = Q.compile(q);
+    t.kind = VT_QUERY, t.a = Q.compile(q, true);
     CP.tmpls.push_back(t);
     return (uint32_t)CP.tmpls.size() - 1;
   }

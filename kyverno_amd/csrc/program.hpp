@@ -42,6 +42,7 @@ struct PatProgram {
 // resource by kpe_cond_kernel. Field names are kept as text: a binding resolves them to corpus
 // D_KEY ids.
 struct CondProgram {
+  bool any_filter = false;  // some query has a filter step `[?P]` (QO_FILT: the kpe_cond_filt_kernel build of the VM)
   std::vector<uint32_t> ops;  // 2 words per op
   std::vector<KpeCExpr> exprs;
   std::vector<KpeVTmpl> tmpls;

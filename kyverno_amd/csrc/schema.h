@@ -696,9 +696,9 @@ typedef struct KpePatRule {
 
 // ---- condition programs (preconditions / deny / foreach-deny; kpe_cond_kernel) -------------
 // A query is the JMESPath expression of a whole-string {{ }} variable (or a foreach `list`),
-// compiled to a linear op list (program.cpp cq::QueryParser): a root, then steps. After `[]`
-// or `[*]` the following steps apply to every element of the projected list; the nulls they
-// produce are dropped when the projection ends (go-jmespath projection semantics).
+// compiled to a linear op list (program.cpp cq::QueryParser): a root, then steps. After `[]`,
+// `[*]` or a filter `[?P]` the following steps apply to every element of the projected list; the
+// nulls they produce are dropped when the projection ends (go-jmespath projection semantics).
 #define QO_OBJ 0u     // request.object: the resource's document root
 #define QO_EL 1u      // element (y = 0xFFFFFFFF: the innermost) / element<y> (foreach nesting y)
 #define QO_IDX 2u     // elementIndex / elementIndex<y> (a float64)
@@ -721,8 +721,38 @@ typedef struct KpePatRule {
 #define QO_FVALS 15u  // values(<chain>) in function form: the member values of an object as a list
                       // (nulls kept); any other type, null included, an invalid-type error
 #define QO_CARG 16u   // an argument of a call expression (CE_CALL): y = the argument's expression
+#define QO_FILT 17u   // `[?P]` over the current value (an array, else the projection is dead): the
+                      // elements P is not false-like for, then projected like `[*]`. QO_ARG = the
+                      // number of predicate ops that follow: P as branch code over its leaves
+#define QO_LEAF 18u   // one leaf of a filter predicate: x = QO_LEAF | FL_* kind << 8 | ops of operand
+                      // A << 16 | ops of operand B << 24, y = FL_T / FL_F: where to go on when the leaf
+                      // is truthy / false-like, an op offset from the predicate's first op, FL_KEEP or
+                      // FL_DROP. Its operand ops follow it, A then B: each starts at the element (`@`)
+                      // and is a QO_CONST (a scalar literal) or a relative QO_FIELD / QO_INDEX chain
+                      // (no op: `@` itself); the B of FL_HASKEY is one QO_FIELD: the member's name
 #define QO_OP(x) ((x) & 0xFFu)
 #define QO_ARG(x) ((x) >> 8)
+// Filter predicate leaves (go-jmespath interpreter.go: comparators, `!` / `&&` / `||` are the
+// branch targets; functions.go jpfContains / jpfStartsWith / jpfEndsWith / jpfKeys)
+#define FL_TRUTHY 0u   // A is not false-like
+#define FL_EQ 1u       // A == B: type-strict deep equality (numbers as float64)
+#define FL_NE 2u
+#define FL_LT 3u       // ordering: null (false-like) unless both sides are numbers
+#define FL_LE 4u
+#define FL_GT 5u
+#define FL_GE 6u
+#define FL_CONTAINS 7u  // contains(A, B) / starts_with / ends_with: their invalid-type errors make
+#define FL_STARTS 8u    // the rule ERROR
+#define FL_ENDS 9u
+#define FL_HASKEY 10u   // contains(keys(A), '<name>'): A not an object is keys()'s invalid-type error
+#define FL_KIND(x) (((x) >> 8) & 0xFFu)
+#define FL_NA(x) (((x) >> 16) & 0xFFu)
+#define FL_NB(x) ((x) >> 24)
+#define FL_T(y) ((y) & 0xFFFFu)
+#define FL_F(y) ((y) >> 16)
+#define FL_KEEP 0xFFFFu
+#define FL_DROP 0xFFFEu
+#define KPE_FILT_LEAVES 16u  // leaves of one predicate (program.cpp refuses more)
 typedef struct KpeCExpr {
   uint32_t op0, nops;  // ops [op0, op0 + nops) (uint2 each)
   uint32_t flags;      // CE_STRICT: a plain field / index chain: a missing member is a NotFoundError

@@ -18,6 +18,7 @@
 
 #define __device__
 #define __forceinline__ inline
+#define KPE_COND_FILT 1   // with filter steps `[?P]` (the build kpe_cond_filt_kernel runs)
 #define KPE_PATVM_CHECK 1  // pattern VM table reads bounds-flagged (foreach pattern entries)
 struct uint2 {
   uint32_t x, y;
