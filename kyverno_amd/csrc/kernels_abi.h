@@ -304,7 +304,9 @@ struct SelMaskArgs {
 #define KPE_LEAN_BATCH 24
 struct LeanShard {
   const uint32_t *rec, *hdr, *crec, *vol, *sys, *pann, *sann;  // the corpus's PSS columns
-  const uint32_t *rec12, *cw4;  // its compact columns (below: 12-byte pod records, container words)
+  // its compact columns (below): 12-byte pod records; container words, or in a scatter launch
+  // the base of the owner-tagged columns (kpe_l6_tag_layout)
+  const uint32_t *rec12, *cw4;
   const uint8_t* codes;  // the corpus's PSA dictionary codes (PsaCodeArgs::codes)
   const uint32_t* kt;     // the binding's kind table: matched-rule mask per kind id (prologue image)
   uint8_t* verdicts;      // n x R
@@ -563,8 +565,69 @@ KPE_L6_FN uint32_t kpe_l6c_pod_split(uint32_t cw, uint32_t tw, uint32_t lists) {
 // kpe_lean_pack_kernel: the compact columns of a corpus, one launch (threads over pods and containers)
 struct LeanPackArgs {
   const uint32_t *rec, *crec;  // n x 4 words, nctr x 2 words
-  uint32_t *rec12, *cw4;       // out: n x 3 words, nctr words
+  uint32_t *rec12, *cw4;       // out: n x 3 words, nctr words (cw4 null: not built)
   uint32_t n, nctr;
+};
+
+// ---- the owner-tagged columns (DeviceCorpus tag, built once per corpus by kpe_lean_tag_kernel):
+// what the scatter form of the compact verdict-only evaluation reads instead of cw4 and the
+// volume, sysctl and annotation columns. Every list item carries its owner, the index of its pod
+// in the pod's 64-pod tile (row & 63), in bits 26-31 of its first word, so the lane that loaded an
+// item can OR the item's evidence into its pod's word without knowing the pod's offsets. The
+// owner is layout (CSR to COO): no code, no evidence, nothing of a policy. A list slot is an item
+// of the tile when its index is below the tile's item count; there is no "real" bit.
+//   container word   states 0-14 and capability-set id 15-25 as in cw4, owner 26-31
+//   sysctl word      id | owner << 26
+//   annotation pair  {key id | owner << 26, value id}
+//   volume word      the source as KPE_L6T_VOL_*, owner 26-31
+// Ids are masked to 26 bits: KPE_NO_STR stays past every dictionary below 2^26 - 1 entries, and a
+// corpus with a larger sysctl or annotation-key dictionary keeps cw4 and the gather form.
+#define KPE_L6T_OWNER_SH 26
+#define KPE_L6T_ID_MASK ((1u << KPE_L6T_OWNER_SH) - 1u)
+static_assert((KPE_L6C_ID_MASK << KPE_L6C_ID_SH) < (1u << KPE_L6T_OWNER_SH), "the owner overlaps the capability-set id");
+KPE_L6_FN uint32_t kpe_l6_tag_owner(uint32_t w) { return w >> KPE_L6T_OWNER_SH; }
+KPE_L6_FN uint32_t kpe_l6_tag_ctr(uint32_t cx, uint32_t cy, uint32_t owner) {
+  return kpe_l6_pack_cx(cx) | ((CY_CAPSET(cy) & KPE_L6C_ID_MASK) << KPE_L6C_ID_SH) | (owner << KPE_L6T_OWNER_SH);
+}
+KPE_L6_FN uint32_t kpe_l6_tag_id(uint32_t id, uint32_t owner) { return (id & KPE_L6T_ID_MASK) | (owner << KPE_L6T_OWNER_SH); }
+KPE_L6_FN uint32_t kpe_l6_tag_get_id(uint32_t w) { return w & KPE_L6T_ID_MASK; }
+// A volume's source mask (VS_* bits, 29 of them) as an index: a volume with exactly one source
+// holds the source's VS_* number, one with none the number 31 (no source has it), and the
+// evaluation decides hostPath / outside the restricted set by shifting two constant masks by the
+// number (kpe_l6_vol_decide: vol_code of the original mask, still taken per step). A volume with
+// several sources has KPE_L6T_VOL_ESC: the evaluation reads its original mask.
+#define KPE_L6T_VOL_IDX 31u  // the index field, and the index of a volume with no source
+#define KPE_L6T_VOL_ESC (1u << 6)
+static_assert(VS_EPHEMERAL < 31, "volume source 31 stands for no source");
+KPE_L6_FN uint32_t kpe_l6_tag_vol(uint32_t src, uint32_t owner) {
+  const uint32_t w = src == 0u ? KPE_L6T_VOL_IDX : (src & (src - 1u)) == 0u ? (uint32_t)__builtin_ctz(src) : KPE_L6T_VOL_ESC;
+  return w | (owner << KPE_L6T_OWNER_SH);
+}
+// vol_code (bit 0 hostPath, bit 1 outside the restricted set) of a volume word without KPE_L6T_VOL_ESC
+KPE_L6_FN uint32_t kpe_l6_vol_decide(uint32_t w) {
+  const uint32_t i = w & KPE_L6T_VOL_IDX;
+  return (((1u << VS_HOSTPATH) >> i) & 1u) | (((~(uint32_t)PSS_ALLOWED_VOLUMES >> i) & 1u) << 1);
+}
+// The four tagged columns in one device allocation (LeanShard::cw4 is its base in a scatter
+// launch): containers at 0, then volumes, sysctls and annotation pairs at 256-byte boundaries,
+// then KPE_L6T_SLACK bytes that the clamped over-reads of the last tile end in.
+#define KPE_L6T_SLACK 1024u
+struct KpeL6TagLayout {
+  uint64_t o_vol, o_sys, o_ann, bytes;  // byte offsets; bytes: the allocation with its slack
+};
+KPE_L6_FN KpeL6TagLayout kpe_l6_tag_layout(uint32_t nctr, uint32_t nvol, uint32_t nsys, uint32_t npann) {
+  KpeL6TagLayout t;
+  t.o_vol = ((uint64_t)nctr * 4u + 255u) & ~(uint64_t)255u;
+  t.o_sys = (t.o_vol + (uint64_t)nvol * 4u + 255u) & ~(uint64_t)255u;
+  t.o_ann = (t.o_sys + (uint64_t)nsys * 4u + 255u) & ~(uint64_t)255u;
+  t.bytes = t.o_ann + (uint64_t)npann * 8u + KPE_L6T_SLACK;
+  return t;
+}
+// kpe_lean_tag_kernel: one wave per 64-pod tile; offsets as in kpe_psum_kernel
+struct LeanTagArgs {
+  const uint32_t *rec, *hdr, *crec, *vol, *sys, *pann;  // the corpus's PSS columns
+  uint32_t* tag;                                        // out: the allocation (kpe_l6_tag_layout)
+  uint32_t n, ntiles, nctr, nvol, nsys, npann;
 };
 
 // kpe_pattern_kernel arguments (device-resident, one copy per binding)

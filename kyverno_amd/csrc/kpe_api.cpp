@@ -426,17 +426,37 @@ kpe_status run_codes(const kpe::Corpus& C, kpe::DeviceCorpus& D, hipStream_t s) 
   D.codes_ready = true;
   return KPE_OK;
 }
-// The LEAN evaluation's compact columns of an uploaded corpus (kpe_lean_pack_kernel, one launch):
-// built where the codes are, for a corpus bound to kpe_lean6_kernel. Both carry 128 bytes of
+// The LEAN evaluation's compact columns of an uploaded corpus: built where the codes are, for a
+// corpus bound to kpe_lean6_kernel. rec12 always (kpe_lean_pack_kernel); then what the device's
+// selected shape reads: the owner-tagged columns of the scatter form (kpe_lean_tag_kernel: one
+// zeroed allocation, kernels_abi.h kpe_l6_tag_layout), or cw4 when `gather` asks for the gather
+// form or the tagged columns cannot hold the corpus (an id dictionary past their 26 bits, or more
+// than 4 GiB of them: the kernel's byte offsets are 32 bits). rec12 and cw4 carry 128 bytes of
 // slack; the kernel's descriptors end at n * 12 and nctr * 4 bytes (loads past those return 0).
-kpe_status run_lean_pack(const kpe::Corpus& C, kpe::DeviceCorpus& D, hipStream_t s) {
+kpe_status run_lean_pack(const kpe::Corpus& C, kpe::DeviceCorpus& D, hipStream_t s, bool gather) {
   LeanPackArgs a{};
   a.n = (uint32_t)C.n, a.nctr = (uint32_t)C.c_sc.size();
+  const uint32_t nvol = (uint32_t)C.vol_src.size(), nsys = (uint32_t)C.sys_id.size();
+  const uint32_t npann = (uint32_t)(C.pann_kv.size() / 2);
+  const KpeL6TagLayout lay = kpe_l6_tag_layout(a.nctr, nvol, nsys, npann);
+  const bool tag = !gather && C.dict[D_SYSCTL].size() < KPE_L6T_ID_MASK && C.dict[D_ANNK].size() < KPE_L6T_ID_MASK &&
+                   lay.bytes < (1ull << 32);
   HIPCHK(D.rec12.ensure((size_t)a.n * 12 + 128));
-  HIPCHK(D.cw4.ensure((size_t)a.nctr * 4 + 128));
+  if (!tag) HIPCHK(D.cw4.ensure((size_t)a.nctr * 4 + 128));
   a.rec = D.rec.as<uint32_t>(), a.crec = D.crec.as<uint32_t>();
-  a.rec12 = D.rec12.as<uint32_t>(), a.cw4 = D.cw4.as<uint32_t>();
+  a.rec12 = D.rec12.as<uint32_t>(), a.cw4 = tag ? nullptr : D.cw4.as<uint32_t>();
   HIPCHK(kpe_launch_lean_pack(&a, s));
+  if (tag) {
+    LeanTagArgs t{};
+    HIPCHK(D.tag.ensure((size_t)lay.bytes));
+    HIPCHK(hipMemsetAsync(D.tag.p, 0, (size_t)lay.bytes, s));
+    t.rec = a.rec, t.hdr = D.hdr.as<uint32_t>(), t.crec = a.crec;
+    t.vol = D.vol_src.as<uint32_t>(), t.sys = D.sys_id.as<uint32_t>(), t.pann = D.pann_kv.as<uint32_t>();
+    t.tag = D.tag.as<uint32_t>();
+    t.n = a.n, t.ntiles = (uint32_t)((C.n + 63) / 64), t.nctr = a.nctr, t.nvol = nvol, t.nsys = nsys, t.npann = npann;
+    HIPCHK(kpe_launch_lean_tag(&t, s));
+  }
+  D.tag_ready = tag, D.cw4_ready = !tag;
   D.pack_ready = true;
   return KPE_OK;
 }
@@ -959,7 +979,7 @@ kpe_status ensure_binding(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc
   if (P.any_pss && !cc->d->codes_ready)
     if (kpe_status st = run_codes(C, *cc->d, s)) return st;
   if (B.lean_kind == KPE_SCAN_LEAN6 && !cc->d->pack_ready)  // and the LEAN evaluation's compact columns
-    if (kpe_status st = run_lean_pack(C, *cc->d, s)) return st;
+    if (kpe_status st = run_lean_pack(C, *cc->d, s, dev->lean_shape & 32u)) return st;
   // the general scan of a podSecurity program reads per-pod PSA records (PSUM instantiation) that
   // kpe_psum_kernel rebuilds before it every time, or (KPE_PSUM=0) walks the pods' lists
   B.gen_code = (narrow ? KPE_SCAN_NARROW : KPE_SCAN_WIDE) | (P.any_pss && !dev->no_psum ? KPE_SCAN_PSUM : 0);
@@ -1027,7 +1047,7 @@ kpe_status launch(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc, bool m
   if (cold && P.any_pss)  // a cold evaluation rebuilds the corpus's PSA dictionary codes too
     if (kpe_status st = run_codes(C, D, s)) return st;
   if (cold && B.lean && B.lean_kind == KPE_SCAN_LEAN6)  // and its compact columns
-    if (kpe_status st = run_lean_pack(C, D, s)) return st;
+    if (kpe_status st = run_lean_pack(C, D, s, dev->lean_shape & 32u)) return st;
   const bool lean_go = B.lean && (!masks || B.lean_kind == KPE_SCAN_LEAN6);  // LEAN6 writes check masks too
   const bool six = lean_go && B.lean_kind == KPE_SCAN_LEAN6;
   const bool psum_go = P.any_pss && !lean_go && !dev->no_psum;  // the PSUM scan and its per-pod records
@@ -1397,10 +1417,18 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
   a.tpw = tpw;
   // the kernel's shape: check masks, or more version classes than the evidence masks hold, take
   // the instantiation that decides every versioned check; the others decide classes, over the
-  // compact columns unless KPE_LEAN6_SHAPE bit 4 asks for the wide records
+  // compact columns unless KPE_LEAN6_SHAPE bit 4 asks for the wide records (bit 5: the gather form
+  // over rec12 / cw4, which is then what the corpora have, not the scatter form)
   const bool cv = masks || PD.ncls > KPE_L6_CLS || (dev->lean_shape & 2u);
   bool cp = kpe_lean6_compact(lc ? 1 : 0, cv ? 1 : 0) && !(dev->lean_shape & 16u);
-  for (size_t k = 0; k < m; ++k) cp = cp && cs[k]->d->pack_ready;
+  // the scatter form when every shard has the owner-tagged columns, else the gather form when
+  // every shard has cw4, else the wide records
+  bool sc = cp, ga = cp;
+  for (size_t k = 0; k < m; ++k) {
+    const auto& D = *cs[k]->d;
+    sc = sc && D.pack_ready && D.tag_ready, ga = ga && D.pack_ready && D.cw4_ready;
+  }
+  cp = sc || ga;
   uint32_t acc = 0, kt_max = 0;
   *bytes = 0;
   for (size_t k = 0; k < m; ++k) {
@@ -1411,7 +1439,7 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
     sh.rec = D.rec.as<uint32_t>(), sh.hdr = D.hdr.as<uint32_t>(), sh.crec = D.crec.as<uint32_t>();
     sh.vol = D.vol_src.as<uint32_t>(), sh.sys = D.sys_id.as<uint32_t>(), sh.pann = D.pann_kv.as<uint32_t>();
     sh.sann = D.c_sann.as<uint32_t>();
-    sh.rec12 = D.rec12.as<uint32_t>(), sh.cw4 = D.cw4.as<uint32_t>();
+    sh.rec12 = D.rec12.as<uint32_t>(), sh.cw4 = (sc ? D.tag : D.cw4).as<uint32_t>();
     sh.codes = D.psa_codes.as<uint8_t>();
     sh.kt = B.pimg.as<uint32_t>() + B.kt_lds;
     sh.verdicts = B.verdicts.as<uint8_t>();
@@ -1439,7 +1467,8 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
   a.pod_tab = (cp ? dev->lean_pod_tab_c : dev->lean_pod_tab).as<uint32_t>();
   const size_t dyn = 4 * ((size_t)KPE_L6_PT_WORDS + a.kt_words + a.code_words + 4 * (size_t)a.wave_words);
   HIPCHK(kpe_launch_lean6(&a, dyn, lc ? 1 : 0, (a.need & NEED_SANN) || (dev->lean_shape & 1u) ? 1 : 0, cv ? 1 : 0,
-                         cp ? 1 : 0, s));
+                         sc ? 2 : cp ? 1 : 0, s));
+  dev->lean_form = sc ? 2 : cp ? 1 : 0;
   return KPE_OK;
 }
 
@@ -1534,7 +1563,7 @@ kpe_status kpe_device_open(int ordinal, kpe_device** out) {
     const int t = atoi(ev);
     d->lean_tpw = t == 1 || t == 2 || t == 4 ? (uint32_t)t : 0u;
   }
-  if (const char* ev = getenv("KPE_LEAN6_SHAPE")) d->lean_shape = (uint32_t)atoi(ev) & 0x13u;
+  if (const char* ev = getenv("KPE_LEAN6_SHAPE")) d->lean_shape = (uint32_t)atoi(ev) & 0x33u;
   for (int k = 0; k < d->nlanes; ++k) {
     e = hipStreamCreateWithFlags(&d->lanes[k], hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -1634,6 +1663,11 @@ int kpe_debug_lean_kind(const kpe_corpus* c, uint64_t lim) {
   if (!c) return -KPE_E_INVALID;
   return lean6_fits(*c->c, lim ? lim : kLean6Limit) ? KPE_SCAN_LEAN6 : KPE_SCAN_LEAN;
 }
+
+// Diagnostic (not in kpe.h): the columns the device's last kpe_lean6_kernel launch read: 0 the
+// wide records, 1 rec12 / cw4 (gather form), 2 the owner-tagged columns (scatter form); -1 before
+// the first launch.
+int kpe_debug_lean_form(const kpe_device* d) { return d ? d->lean_form : -KPE_E_INVALID; }
 
 kpe_status kpe_corpus_row_flags(const kpe_corpus* c, uint32_t* out) {
   if (!c || !out) return fail(KPE_E_INVALID, "kpe_corpus_row_flags: null argument");

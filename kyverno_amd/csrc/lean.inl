@@ -45,8 +45,10 @@ __device__ __forceinline__ const __attribute__((address_space(4))) void* kargs()
 #endif
 // The verdict-only form over the compact columns (CP) holds a container in one register, not two,
 // and is compiled for eight resident blocks per CU: 64 VGPRs and, by the rule below, 80 SGPRs
-// (<4, true, false, false, true>: 60 VGPRs, no scratch, nine scalars kept in lanes). The seccomp
-// annotation form spills 13 VGPRs to scratch at eight and stays at seven.
+// (gather form <4, true, false, false, true>: 60 VGPRs, no scratch, nine scalars kept in lanes;
+// scatter form <..., true>: 50 VGPRs, 77 SGPRs, none). The gather form with the seccomp annotations
+// spills 13 VGPRs to scratch at eight and stays at seven; so does the scatter form with them
+// (58 VGPRs, 80 SGPRs), which shares the setting and measured no faster at eight.
 #ifndef KPE_LEAN6C_WAVES
 #define KPE_LEAN6C_WAVES 8
 #endif
@@ -243,9 +245,43 @@ __global__ void __launch_bounds__(256) kpe_lean_pack_kernel(LeanPackArgs a) {
     uint32_t* const o = a.rec12 + 3u * (size_t)i;
     o[0] = r.x, o[1] = r.y, o[2] = r.z;
   }
-  if (i < a.nctr) {
+  if (a.cw4 && i < a.nctr) {
     const uint2 e = reinterpret_cast<const uint2*>(a.crec)[i];
     a.cw4[i] = kpe_l6_pack_ctr(e.x, e.y);
+  }
+}
+
+// ---- kpe_lean_tag_kernel: the owner-tagged columns of a corpus (once per corpus) ---------------
+// One wave per 64-pod tile, launched where kpe_lean_pack_kernel is: lane i finds pod i's list
+// offsets as kpe_psum_kernel does (tile header plus a wave scan of the packed counts) and writes
+// each of its items with owner i (kernels_abi.h kpe_l6_tag_*). An item outside its column (counts
+// and headers that disagree) is not written; the allocation is zeroed before the launch.
+__global__ void __launch_bounds__(256) kpe_lean_tag_kernel(LeanTagArgs a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (tile >= a.ntiles) return;
+  const uint32_t r = tile * 64u + lane;
+  const uint32_t h = a.hdr[tile * 4u + (lane & 3u)];
+  const uint32_t z = r < a.n ? a.rec[4u * (size_t)r + 2u] : 0u;
+  const uint32_t nc = PRC_CTR(z), nv = PRC_VOL(z), ns = PRC_SYS(z), na = PRC_PANN(z);
+  const uint32_t c01 = nc | (nv << 16), c23 = ns | (na << 16);
+  const uint32_t e01 = wave_incl_scan(c01) - c01, e23 = wave_incl_scan(c23) - c23;
+  const uint32_t oc = hw(h, 0) + (e01 & 0xFFFFu), ov = hw(h, 1) + (e01 >> 16), os = hw(h, 2) + (e23 & 0xFFFFu),
+                 oa = hw(h, 3) + (e23 >> 16);
+  const KpeL6TagLayout t = kpe_l6_tag_layout(a.nctr, a.nvol, a.nsys, a.npann);
+  uint32_t* const tc = a.tag;
+  uint32_t* const tv = a.tag + (t.o_vol >> 2);
+  uint32_t* const ts = a.tag + (t.o_sys >> 2);
+  uint32_t* const ta = a.tag + (t.o_ann >> 2);
+  for (uint32_t k = oc; k < oc + nc && k < a.nctr; ++k) {
+    const uint2 e = reinterpret_cast<const uint2*>(a.crec)[k];
+    tc[k] = kpe_l6_tag_ctr(e.x, e.y, lane);
+  }
+  for (uint32_t k = ov; k < ov + nv && k < a.nvol; ++k) tv[k] = kpe_l6_tag_vol(a.vol[k], lane);
+  for (uint32_t k = os; k < os + ns && k < a.nsys; ++k) ts[k] = kpe_l6_tag_id(a.sys[k], lane);
+  for (uint32_t k = oa; k < oa + na && k < a.npann; ++k) {
+    const uint2 q = reinterpret_cast<const uint2*>(a.pann)[k];
+    ta[2u * (size_t)k] = kpe_l6_tag_id(q.x, lane), ta[2u * (size_t)k + 1u] = q.y;
   }
 }
 
@@ -273,6 +309,8 @@ __global__ void __launch_bounds__(256) kpe_lean_pack_kernel(LeanPackArgs a) {
 // (kpe_lean_pack_kernel above) and the evidence word is decided in the packed numbering
 // (kernels_abi.h KPE_L6C_*: the host passes the class masks and the pod table permuted by
 // kpe_l6_pack_ev). The slow-path loops read cw4 too. The CV forms keep the wide records.
+// SC (the default of CP): the scatter form over the owner-tagged columns, l6_scatter_tiles below;
+// l6_gather_tiles, CP, is then the gather form, KPE_LEAN6_SHAPE bit 5.
 typedef const __attribute__((address_space(4))) LeanBatchArgs CBArgs;
 typedef const __attribute__((address_space(4))) LeanShard CShard;
 // CT: a loaded container, the wide record (uint2) or the compact word (uint32_t)
@@ -291,10 +329,9 @@ struct L6Items<true, CT> : L6Items<false, CT> {
 // sysctl code (bit v: outside version v's set) at its evidence bits
 __device__ __forceinline__ uint32_t l6_sys_evidence(uint32_t c) { return ((c & 3u) << 1) | ((c & 4u) << 2); }
 
-template <int T, bool LC, bool SANN, bool CV, bool CP = false>
-__global__ void __launch_bounds__(kLB, l6_waves(SANN, CP)) __attribute__((amdgpu_num_sgpr(KPE_LEAN6_SGPRS)))
-kpe_lean6_kernel(LeanBatchArgs) {
-  static_assert(!(CP && CV), "the compact columns are read by the verdict-only form");
+// The body of every form but the scatter form (the kernel itself: end of this file)
+template <int T, bool LC, bool SANN, bool CV, bool CP>
+__device__ __forceinline__ void l6_gather_tiles() {
   typedef typename std::conditional<CP, uint32_t, uint2>::type CT;
   extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
   CBArgs& a = *(CBArgs*)kargs();
@@ -616,4 +653,257 @@ kpe_lean6_kernel(LeanBatchArgs) {
     __builtin_amdgcn_wave_barrier();
     if (!stored) store_rows(S.verdicts, sv, tile, R, 0, R, nrows, lane);
   }
+}
+
+// ---- kpe_lean6_kernel<T, true, SANN, false, true, true>: the scatter form of the compact
+// verdict-only evaluation. The same launch shape, memory steps 1 and 2, class decision and row
+// packing as the gather form <T, true, SANN, false, true>, over the corpus's owner-tagged columns
+// (kernels_abi.h kpe_l6_tag_*; LeanShard::cw4 is the base of the one allocation that holds the
+// four, read through one descriptor plus scalar byte offsets). No pod gathers its items: the lane
+// that loaded an item codes it exactly as the gather form does, shifts the code to its place in
+// the packed evidence word and ORs it into the word of the item's owner in LDS (one ds_or_b32
+// per 64 slots; the packed word is an OR over disjoint bit ranges, and kpe_l6c_pod_split clears
+// only container-state bits). A slot whose index is not below the tile's item count ORs 0: it
+// holds an item of the next tile, whose owner names a pod of this one, or bytes of the next
+// column or the slack. A tile with more items than the loaded slots takes further 64-slot
+// batches in a wave-uniform loop. Then pod i reads word i.
+// The shard search, the LDS tables, the class decision and the row packing are l6_gather_tiles's,
+// restated here and to be kept in step with it: as shared __forceinline__ helpers they cost the
+// C2 instantiations scalar spills at eight blocks per CU (gather 9 -> 20-25, scatter 0 -> 8-14;
+// DESIGN.md section 9).
+template <int T, bool SANN>
+__device__ __forceinline__ void l6_scatter_tiles() {
+  extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
+  CBArgs& a = *(CBArgs*)kargs();
+  const uint32_t t = threadIdx.x, lane = t & 63u;
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const uint32_t gb = xcd_block(blockIdx.x, gridDim.x);
+  uint32_t lo = 0, hi = a.nshards;  // blk0[lo] <= gb < blk0[hi]
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a.blk0[mid] <= gb) lo = mid;
+    else hi = mid;
+  }
+  CShard& S = a.sh[lo];
+  const uint32_t n = S.n, ntiles = (n + 63u) >> 6;
+  const uint32_t tile0 = ((gb - a.blk0[lo]) * 4u + wv) * (uint32_t)T;
+  const uint32_t need = a.need;
+  const bool nvol = need & NEED_VOL, nsys = need & NEED_SYS, npann = need & NEED_PANN;
+  const Rsrc REC = make_rsrc(S.rec12, n * 12u);
+  const Rsrc HDR = make_rsrc(S.hdr, (ntiles + 1u) * 16u);
+  // every load of the tagged columns lies inside the allocation (slack included): what a slot
+  // past a tile's count holds is dropped by the count, not by the descriptor
+  const KpeL6TagLayout lay = kpe_l6_tag_layout(S.nctr, S.nvol, S.nsys, S.npann);
+  const Rsrc TAG = make_rsrc(S.cw4, (uint32_t)lay.bytes);
+  const uint32_t o_vol = (uint32_t)lay.o_vol, o_sys = (uint32_t)lay.o_sys, o_ann = (uint32_t)lay.o_ann;
+  const Rsrc SAN = make_rsrc(S.sann, SANN && (need & NEED_SANN) ? S.nctr * 4u : 0u);
+  const uint32_t l4 = lane * 4u;
+  auto ldt = [&](uint32_t voff, uint32_t soff) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(TAG, voff, soff, 0); };
+  // ---- step 1: headers and records (words x and y; the packed counts are not read)
+  const uint32_t hall = bload1(HDR, (tile0 * 4u + min(lane, 4u * T + 3u)) * 4u);
+  uint2 rec[T];
+#pragma unroll
+  for (int j = 0; j < T; ++j) rec[j] = bload2(REC, ((tile0 + j) * 64u + lane) * 12u);  // past n: zeros
+  const uint32_t nk = S.nkinds;
+  const uint32_t k0 = t < nk ? S.kt[t] : 0u;
+  const uint32_t ncw = (S.L.bytes + 3u) >> 2;
+  const uint32_t* gcw = reinterpret_cast<const uint32_t*>(S.codes);
+  const uint32_t cw0 = t < ncw ? gcw[t] : 0u;
+  const uint32_t* const gpt = a.pod_tab;
+  const uint32_t pt0 = gpt[t];
+  const uint32_t pt1 = t < KPE_L6_PT_WORDS - kLB ? gpt[t + kLB] : 0u;
+  // ---- step 2: the list items of every tile
+  L6Items<SANN, uint32_t> it[T];
+#pragma unroll
+  for (int j = 0; j < T; ++j) {
+    if (tile0 + j >= ntiles) break;
+    const uint32_t C0 = hw(hall, 4u * j), V0 = hw(hall, 4u * j + 1u), S0 = hw(hall, 4u * j + 2u),
+                   A0 = hw(hall, 4u * j + 3u);
+    it[j].c0 = ldt(l4, C0 * 4u);
+    it[j].c1 = ldt(l4 + 256u, C0 * 4u);
+    if constexpr (SANN) {
+      it[j].a0 = bload1(SAN, (C0 + lane) * 4u);
+      it[j].a1 = bload1(SAN, (C0 + 64u + lane) * 4u);
+    }
+    it[j].v0 = it[j].v1 = it[j].s0 = 0u;
+    it[j].q0 = make_uint2(0u, 0u);
+    if (nvol) it[j].v0 = ldt(l4, o_vol + V0 * 4u), it[j].v1 = ldt(l4 + 256u, o_vol + V0 * 4u);
+    if (nsys) it[j].s0 = ldt(l4, o_sys + S0 * 4u);
+    if (npann) {
+      const auto q = __builtin_amdgcn_raw_buffer_load_b64(TAG, lane * 8u, o_ann + A0 * 8u, 0);
+      it[j].q0 = make_uint2(q[0], q[1]);
+    }
+  }
+  dyn[t] = pt0;
+  if (t < KPE_L6_PT_WORDS - kLB) dyn[t + kLB] = pt1;
+  uint32_t* const kt = dyn + KPE_L6_PT_WORDS;
+  if (t < nk) kt[t] = k0;
+#pragma unroll 1
+  for (uint32_t i = t + kLB; i < nk; i += kLB) kt[i] = S.kt[i];
+  uint32_t* const cl = kt + a.kt_words;
+  if (t < ncw) cl[t] = cw0;
+#pragma unroll 1
+  for (uint32_t i = t + kLB; i < ncw; i += kLB) cl[i] = gcw[i];
+  const uint32_t ncls = a.ncls;
+  __syncthreads();
+  const uint8_t* const lcodes = reinterpret_cast<const uint8_t*>(cl);
+  auto cb = [&](uint32_t i) -> uint32_t { return (uint32_t)lcodes[i]; };
+  PsaCodes L;
+  L.ncapsets = S.L.ncapsets, L.nsysd = S.L.nsysd, L.nannk = S.L.nannk, L.nannv = S.L.nannv;
+  L.o_sys = S.L.o_sys, L.o_annk = S.L.o_annk, L.o_annv = S.L.o_annv, L.bytes = S.L.bytes;
+  const PsaCoder K{L};
+  uint32_t cev[KPE_L6_CLS], cev_nw[KPE_L6_CLS], crm[KPE_L6_CLS];
+#pragma unroll
+  for (uint32_t c = 0; c < KPE_L6_CLS; ++c) {
+    cev[c] = a.cls_ev[c], cev_nw[c] = a.cls_ev_nw[c], crm[c] = a.cls_rm[c];
+    asm volatile("" : "+s"(cev[c]), "+s"(cev_nw[c]), "+s"(crm[c]));
+  }
+  const uint32_t R = a.nrules, pss_rules = a.pss_rules;
+  const uint32_t ep_rules = a.err_rules | a.pat_rules, pat_rules = a.pat_rules;
+  // the wave's stage (laid out as the gather form's): the 64 evidence words first, the rows last
+  uint8_t* const stg = reinterpret_cast<uint8_t*>(cl + a.code_words + wv * a.wave_words);
+  uint32_t* const acc = reinterpret_cast<uint32_t*>(stg);
+  uint8_t* const sv = stg + KPE_L6_STAGE_BYTES;  // the tile's verdict rows (64 x R bytes; 256 at least)
+  const bool rpack = R - 2u <= 2u;  // rows of 2 to 4 bytes leave as one dword store per lane (as in the gather form)
+  uint32_t rp_cell = 0, rp_sel = 0;
+  if (rpack) {
+    const uint32_t b = 4u * lane, p0 = R == 3u ? (b * 171u) >> 9 : b >> (R >> 1), r0 = b - p0 * R;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+      const uint32_t g = r0 + k;
+      rp_sel |= (g >= R ? 4u + g - R : g) << (8u * k);
+    }
+    rp_cell = min(p0, 63u);
+  }
+  // evidence `ev` of the item whose first word is w, into its owner's word; 0 from a slot that is
+  // no item of the tile
+  auto put = [&](uint32_t w, uint32_t ev, bool valid) {
+    __hip_atomic_fetch_or(acc + kpe_l6_tag_owner(w), valid ? ev : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+  };
+  auto ctr_ev = [&](uint32_t e, uint32_t cs) -> uint32_t {
+    uint32_t w = (e & ((1u << KPE_L6C_STATES) - 1u)) | ((cb(kpe_l6_ctr_capset(e)) & 7u) << KPE_L6C_CAP_SH);
+    if constexpr (SANN) w |= K.sann(cb, cs) << KPE_L6C_SANN_SH;
+    return w;
+  };
+#pragma unroll
+  for (int j = 0; j < T; ++j) {
+    const uint32_t tile = tile0 + j;
+    if (tile >= ntiles) break;
+    const L6Items<SANN, uint32_t>& d = it[j];
+    const uint32_t C0 = hw(hall, 4u * j), V0 = hw(hall, 4u * j + 1u), S0 = hw(hall, 4u * j + 2u),
+                   A0 = hw(hall, 4u * j + 3u);
+    const uint32_t nct = hw(hall, 4u * j + 4u) - C0, nvt = hw(hall, 4u * j + 5u) - V0,
+                   nst = hw(hall, 4u * j + 6u) - S0, nat = hw(hall, 4u * j + 7u) - A0;
+    const uint32_t r = tile * 64u + lane;
+    const bool live = r < n;
+    __builtin_amdgcn_wave_barrier();  // the previous tile's words are read
+    acc[lane] = 0u;
+    __builtin_amdgcn_wave_barrier();
+    {  // containers: slots lane and 64 + lane, then batches of 64
+      uint32_t a0 = 0, a1 = 0;
+      if constexpr (SANN) a0 = d.a0, a1 = d.a1;
+      put(d.c0, ctr_ev(d.c0, a0), lane < nct);
+      put(d.c1, ctr_ev(d.c1, a1), lane + 64u < nct);
+#pragma unroll 1
+      for (uint32_t b = KPE_L6_CTR; b < nct; b += 64u) {
+        const uint32_t e = ldt(l4, (C0 + b) * 4u);
+        const uint32_t cs = SANN ? bload1(SAN, (C0 + b + lane) * 4u) : 0u;
+        put(e, ctr_ev(e, cs), b + lane < nct);
+      }
+    }
+    if (nvol && nvt) {
+      // the volume decision; a volume of several sources: vol_code of its original mask
+      auto vol_ev = [&](uint32_t w, uint32_t slot) -> uint32_t {
+        uint32_t c = kpe_l6_vol_decide(w);
+        const bool esc = slot < nvt && (w & KPE_L6T_VOL_ESC);
+        if (__builtin_amdgcn_ballot_w64(esc)) {
+          if (esc) c = vol_code(S.vol[V0 + slot]);
+        }
+        return c << KPE_L6C_VOL_SH;
+      };
+      put(d.v0, vol_ev(d.v0, lane), lane < nvt);
+      put(d.v1, vol_ev(d.v1, lane + 64u), lane + 64u < nvt);
+#pragma unroll 1
+      for (uint32_t b = KPE_L6_VOL; b < nvt; b += 64u) {
+        const uint32_t w = ldt(l4, o_vol + (V0 + b) * 4u);
+        put(w, vol_ev(w, b + lane), b + lane < nvt);
+      }
+    }
+    if (nsys && nst) {
+      put(d.s0, K.sys(cb, kpe_l6_tag_get_id(d.s0)) << KPE_L6C_SYS_SH, lane < nst);
+#pragma unroll 1
+      for (uint32_t b = KPE_L6_SMALL; b < nst; b += 64u) {
+        const uint32_t w = ldt(l4, o_sys + (S0 + b) * 4u);
+        put(w, K.sys(cb, kpe_l6_tag_get_id(w)) << KPE_L6C_SYS_SH, b + lane < nst);
+      }
+    }
+    if (npann && nat) {
+      put(d.q0.x, K.ann(cb, make_uint2(kpe_l6_tag_get_id(d.q0.x), d.q0.y)) << KPE_L6C_ANN_SH, lane < nat);
+#pragma unroll 1
+      for (uint32_t b = KPE_L6_SMALL; b < nat; b += 64u) {
+        const auto q = __builtin_amdgcn_raw_buffer_load_b64(TAG, lane * 8u, o_ann + (A0 + b) * 8u, 0);
+        put(q[0], K.ann(cb, make_uint2(kpe_l6_tag_get_id(q[0]), q[1])) << KPE_L6C_ANN_SH, b + lane < nat);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t cw = acc[lane];
+    // ---- the version classes, the rule match (kind table) and the verdict bytes: as the gather form
+    const uint32_t pw = rec[j].x;
+    uint32_t failr = 0;
+    const uint32_t tw = kpe_l6_pod_lookup(dyn, pw);
+    const uint32_t ev = kpe_l6c_pod_split(cw, tw, 0u);
+    const uint32_t ev_nw = ev & (uint32_t)((int32_t)tw >> 31);  // KPE_L6_PT_NW over the word
+#pragma unroll
+    for (uint32_t c = 0; c < KPE_L6_CLS; ++c) {
+      if (c >= ncls) break;
+      const uint32_t hit = (ev & cev[c]) | (ev_nw & cev_nw[c]);
+      uint32_t m = hit ? ~0u : 0u;
+      asm("" : "+v"(m));  // keeps the select on inline constants (see the gather form)
+      failr |= m & crm[c];
+    }
+    const uint32_t cls = (pw >> PR_CLASS_SH) & R_CLASS_MASK;
+    const bool err = cls == R_CLASS_OTHER || (pw & PR_DECODE_ERR);
+    const uint32_t kind = GVK_KIND(rec[j].y);
+    const uint32_t matched = live && kind < nk ? kt[kind] : 0u;
+    const uint32_t E = matched & ((err ? pss_rules : 0u) | ep_rules);
+    const uint32_t F = (matched & pss_rules & failr & ~E) | (matched & pat_rules);  // F|E = PENDING
+    const uint32_t P = matched & pss_rules & ~failr & ~E;
+    const uint32_t nrows = min(64u, n - tile * 64u);
+    bool stored = false;
+    if (R <= 4u) {  // the row as one word, byte ri = rule ri's cell
+      constexpr uint32_t kSpread = 0x204081u, kOnes = 0x01010101u;
+      const uint32_t cellw = (__umul24(P, kSpread) & kOnes) | (__umul24(F, kSpread << 1) & (kOnes << 1)) |
+                             (__umul24(E, kSpread << 2) & (kOnes << 2));
+      if (rpack && nrows == 64u) {
+        uint32_t* const sw = reinterpret_cast<uint32_t*>(sv);
+        sw[lane] = cellw;
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t w0 = sw[rp_cell], w1 = sw[min(rp_cell + 1u, 63u)];
+        if (lane < 16u * R)
+          reinterpret_cast<uint32_t*>(S.verdicts + (size_t)tile * (64u * R))[lane] = __builtin_amdgcn_perm(w1, w0, rp_sel);
+        stored = true;
+      } else {
+#pragma unroll
+        for (uint32_t ri = 0; ri < 4u; ++ri)
+          if (ri < R) sv[lane * R + ri] = (uint8_t)(cellw >> (8u * ri));
+      }
+    } else {
+#pragma unroll 1
+      for (uint32_t ri = 0; ri < R; ++ri)
+        sv[lane * R + ri] = (uint8_t)(((P >> ri) & 1u) | (((F >> ri) & 1u) << 1) | (((E >> ri) & 1u) << 2));
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (!stored) store_rows(S.verdicts, sv, tile, R, 0, R, nrows, lane);
+  }
+}
+
+// SC: the scatter form of CP over the corpus's owner-tagged columns (l6_scatter_tiles); each
+// instantiation holds the one body it runs.
+template <int T, bool LC, bool SANN, bool CV, bool CP = false, bool SC = false>
+__global__ void __launch_bounds__(kLB, l6_waves(SANN, CP)) __attribute__((amdgpu_num_sgpr(KPE_LEAN6_SGPRS)))
+kpe_lean6_kernel(LeanBatchArgs) {
+  static_assert(!(CP && CV), "the compact columns are read by the verdict-only form");
+  static_assert(!SC || (CP && LC), "the scatter form is a compact form with the code bytes in LDS");
+  if constexpr (SC) l6_scatter_tiles<T, SANN>();
+  else l6_gather_tiles<T, LC, SANN, CV, CP>();
 }

@@ -1255,13 +1255,16 @@ extern "C" hipError_t kpe_launch_selmask(const SelMaskArgs* a, hipStream_t s) {
 // than KPE_L6_CLS version classes). Without the code bytes in LDS (rare: > 8 KiB of codes) the
 // one instantiation that covers every program runs.
 // cp: the verdict-only form reads the compact columns (LeanShard::rec12 / cw4; class masks and pod
-// table in the packed numbering); kpe_lean6_compact says which launches may ask for it.
+// table in the packed numbering); kpe_lean6_compact says which launches may ask for it. cp == 2:
+// the scatter form over the owner-tagged columns (SC; LeanShard::cw4 is their base).
 template <int T, bool LC>
 static void lean6_go(int sann, int cv, int cp, dim3 g, dim3 b, size_t dyn_bytes, hipStream_t s, const LeanBatchArgs& a) {
   if constexpr (!LC) {
     hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, true>), g, b, dyn_bytes, s, a);
   } else {
-    if (sann && cv) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, true>), g, b, dyn_bytes, s, a);
+    if (cp == 2 && sann) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, false, true, true>), g, b, dyn_bytes, s, a);
+    else if (cp == 2) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, false, false, true, true>), g, b, dyn_bytes, s, a);
+    else if (sann && cv) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, true>), g, b, dyn_bytes, s, a);
     else if (sann && cp) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, false, true>), g, b, dyn_bytes, s, a);
     else if (sann) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, false>), g, b, dyn_bytes, s, a);
     else if (cv) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, false, true>), g, b, dyn_bytes, s, a);
@@ -1290,6 +1293,12 @@ extern "C" hipError_t kpe_launch_lean_pack(const LeanPackArgs* a, hipStream_t s)
   const uint32_t m = std::max(a->n, a->nctr);
   if (m == 0) return hipSuccess;
   hipLaunchKernelGGL(kpe_lean_pack_kernel, dim3((m + 255u) / 256u), dim3(256), 0, s, *a);
+  return hipGetLastError();
+}
+// The owner-tagged columns of a corpus (lean.inl), one wave per 64-pod tile.
+extern "C" hipError_t kpe_launch_lean_tag(const LeanTagArgs* a, hipStream_t s) {
+  if (a->ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(kpe_lean_tag_kernel, dim3((a->ntiles + 3u) / 4u), dim3(256), 0, s, *a);
   return hipGetLastError();
 }
 // The PSA dictionary codes of a corpus (lean.inl), one launch.
