@@ -147,7 +147,8 @@ struct kpe_device {
   // decides every versioned check, for programs that need neither; bit 4, i.e. 16: the
   // verdict-only form reads the wide records, not the corpus's compact columns; bit 5, i.e. 32:
   // the compact form gathers each pod's items from rec12 / cw4, not the scatter form over the
-  // owner-tagged columns)
+  // owner-tagged columns; bit 6, i.e. 64: scatter launches of two or four tiles per wave read
+  // rec12 as those of one tile do, not the pod word column pw4)
   bool no_cache = false, patvm_err = false;
   // the general scan of a podSecurity program walks each pod's lists itself; KPE_PSUM=1: it reads
   // per-pod records kpe_psum_kernel builds right before it on the second stream (round 6: C4 step
@@ -157,6 +158,7 @@ struct kpe_device {
   uint64_t lean_min_waves = 16384;  // 256 CUs x 4 SIMDs x 16 waves
   uint32_t lean_tpw = 0, lean_shape = 0;
   int lean_form = -1;  // what the last kpe_lean6_kernel launch read (kpe_debug_lean_form)
+  int lean_narrow = 0;  // and whether it was the narrow scatter form (kpe_debug_lean_narrow)
   // kpe_lean6_kernel's pod-evidence table (kernels_abi.h kpe_l6_pod_table_word), built at
   // kpe_device_open: it depends on neither the policies nor a corpus
   kpe::DevBuf lean_pod_tab;
@@ -295,6 +297,10 @@ struct DeviceCorpus {
   // per container; kernels_abi.h), built with the codes for a corpus whose binding is LEAN6
   DevBuf rec12, cw4;
   bool pack_ready = false;
+  // the pod word column (kernels_abi.h kpe_l6_pack_pod), written beside rec12 for a corpus of at
+  // most KPE_L6P_MAX_KINDS kinds: what scatter launches of two or four tiles per wave read of a pod
+  DevBuf pw4;
+  bool pw4_ready = false;
   // its owner-tagged columns (kpe_lean_tag_kernel: one allocation, kernels_abi.h kpe_l6_tag_layout),
   // read by the scatter form of the compact evaluation. A device builds these or cw4, whichever
   // its selected shape reads (KPE_LEAN6_SHAPE bit 5); a corpus they cannot hold keeps cw4.

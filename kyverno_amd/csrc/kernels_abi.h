@@ -305,7 +305,8 @@ struct SelMaskArgs {
 struct LeanShard {
   const uint32_t *rec, *hdr, *crec, *vol, *sys, *pann, *sann;  // the corpus's PSS columns
   // its compact columns (below): 12-byte pod records; container words, or in a scatter launch
-  // the base of the owner-tagged columns (kpe_l6_tag_layout)
+  // the base of the owner-tagged columns (kpe_l6_tag_layout). In a narrow scatter launch rec12
+  // is the pod word column pw4 (below; the struct has no room for a pointer more: 4 KiB)
   const uint32_t *rec12, *cw4;
   const uint8_t* codes;  // the corpus's PSA dictionary codes (PsaCodeArgs::codes)
   const uint32_t* kt;     // the binding's kind table: matched-rule mask per kind id (prologue image)
@@ -562,10 +563,39 @@ KPE_L6_FN uint32_t kpe_l6_pack_ev(uint32_t ev) {
 KPE_L6_FN uint32_t kpe_l6c_pod_split(uint32_t cw, uint32_t tw, uint32_t lists) {
   return (cw & ~(tw & KPE_L6C_PT_CLR)) | (tw & ~(KPE_L6C_PT_CLR | KPE_L6_PT_NW)) | lists;
 }
+// ---- the pod word column pw4 (DeviceCorpus pw4, written by kpe_lean_pack_kernel beside rec12):
+// what the scatter form reads of a pod record, in one word. Of x that is bits 1-22 (the three
+// slices kpe_l6_pod_lookup indexes with, the class at PR_CLASS_SH and PR_DECODE_ERR), of y the
+// kind id; the packed counts z are not read at all. Layout only, as rec12: no code, no evidence,
+// nothing of a policy. Built for a corpus whose kind dictionary has at most KPE_L6P_MAX_KINDS
+// entries (the kind id's 10 bits); any other corpus keeps rec12 alone.
+//   table slices 0-6, 7-14, 15-18   class 19-20   decode error 21   kind id 22-31
+#define KPE_L6P_X_BITS 22u
+#define KPE_L6P_B_SH 7
+#define KPE_L6P_C_SH 15
+#define KPE_L6P_CLASS_SH 19
+#define KPE_L6P_DECODE_ERR (1u << 21)
+#define KPE_L6P_KIND_SH 22
+#define KPE_L6P_MAX_KINDS 1024u
+static_assert(P_HOSTNET == (1u << 1) && P_OS_SH + 2 == 20 && P_SECCOMP_SH == KPE_L6P_B_SH + 1 && P_WHP_SH == KPE_L6P_C_SH + 1,
+              "pw4's table slices are bits 1-7, 8-15 and 16-19 of the pod word, shifted down by one");
+static_assert(PR_CLASS_SH == KPE_L6P_CLASS_SH + 1 && R_CLASS_MASK == 3u && PR_DECODE_ERR == (KPE_L6P_DECODE_ERR << 1) &&
+                  KPE_L6P_KIND_SH == KPE_L6P_X_BITS,
+              "pw4's class and decode error are bits 20-22 of the pod word, shifted down by one");
+KPE_L6_FN uint32_t kpe_l6_pack_pod(uint32_t x, uint32_t y) {
+  return ((x >> 1) & ((1u << KPE_L6P_X_BITS) - 1u)) | (GVK_KIND(y) << KPE_L6P_KIND_SH);
+}
+// kpe_l6_pod_lookup of the pod word a pw4 word was packed from
+KPE_L6_FN uint32_t kpe_l6p_pod_lookup(const uint32_t* tab, uint32_t w) {
+  return tab[w & 127u] | tab[KPE_L6_PT_B0 + ((w >> KPE_L6P_B_SH) & 255u)] | tab[KPE_L6_PT_C0 + ((w >> KPE_L6P_C_SH) & 15u)];
+}
+KPE_L6_FN uint32_t kpe_l6p_class(uint32_t w) { return (w >> KPE_L6P_CLASS_SH) & R_CLASS_MASK; }
+KPE_L6_FN uint32_t kpe_l6p_kind(uint32_t w) { return w >> KPE_L6P_KIND_SH; }
 // kpe_lean_pack_kernel: the compact columns of a corpus, one launch (threads over pods and containers)
 struct LeanPackArgs {
   const uint32_t *rec, *crec;  // n x 4 words, nctr x 2 words
   uint32_t *rec12, *cw4;       // out: n x 3 words, nctr words (cw4 null: not built)
+  uint32_t* pw4;               // out: n words (null: not built, more than KPE_L6P_MAX_KINDS kinds)
   uint32_t n, nctr;
 };
 

@@ -441,11 +441,17 @@ kpe_status run_lean_pack(const kpe::Corpus& C, kpe::DeviceCorpus& D, hipStream_t
   const KpeL6TagLayout lay = kpe_l6_tag_layout(a.nctr, nvol, nsys, npann);
   const bool tag = !gather && C.dict[D_SYSCTL].size() < KPE_L6T_ID_MASK && C.dict[D_ANNK].size() < KPE_L6T_ID_MASK &&
                    lay.bytes < (1ull << 32);
+  // the pod word column beside rec12 where the kind ids fit its 10 bits (128 bytes of slack; the
+  // kernel's descriptor ends at n * 4 bytes)
+  const bool pw4 = C.dict[D_KIND].size() <= KPE_L6P_MAX_KINDS;
   HIPCHK(D.rec12.ensure((size_t)a.n * 12 + 128));
+  if (pw4) HIPCHK(D.pw4.ensure((size_t)a.n * 4 + 128));
   if (!tag) HIPCHK(D.cw4.ensure((size_t)a.nctr * 4 + 128));
   a.rec = D.rec.as<uint32_t>(), a.crec = D.crec.as<uint32_t>();
   a.rec12 = D.rec12.as<uint32_t>(), a.cw4 = tag ? nullptr : D.cw4.as<uint32_t>();
+  a.pw4 = pw4 ? D.pw4.as<uint32_t>() : nullptr;
   HIPCHK(kpe_launch_lean_pack(&a, s));
+  D.pw4_ready = pw4;
   if (tag) {
     LeanTagArgs t{};
     HIPCHK(D.tag.ensure((size_t)lay.bytes));
@@ -483,11 +489,12 @@ kpe_status run_psum(const kpe::Corpus& C, kpe::DeviceCorpus& D, hipStream_t s, u
 // Algorithmic bytes of one LEAN evaluation of a shard (kpe_lean6_kernel): the pod records, the tile
 // headers, the list columns the program reads, the code bytes and kind table its blocks stage
 // (counted once), the verdict cells and, in the masks mode, the check masks. compact: the launch
-// reads the 12-byte pod records and the 4-byte container words.
+// reads the 12-byte pod records and the 4-byte container words; narrow: a compact (scatter) launch
+// that reads the 4-byte pod words instead.
 double lean_bytes(const kpe::Corpus& C, const kpe::DeviceCorpus& D, uint32_t need, uint32_t R, bool masks,
-                  bool compact = false) {
+                  bool compact = false, bool narrow = false) {
   const double n = (double)C.n;
-  double b = (compact ? 12.0 : 16.0) * n + 16.0 * (double)((C.n + 63) / 64 + 1) +
+  double b = (narrow ? 4.0 : compact ? 12.0 : 16.0) * n + 16.0 * (double)((C.n + 63) / 64 + 1) +
              (compact ? 4.0 : 8.0) * (double)C.c_sc.size();
   if (need & NEED_SANN) b += 4.0 * (double)C.c_sc.size();
   if (need & NEED_VOL) b += 4.0 * (double)C.vol_src.size();
@@ -1423,12 +1430,16 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
   bool cp = kpe_lean6_compact(lc ? 1 : 0, cv ? 1 : 0) && !(dev->lean_shape & 16u);
   // the scatter form when every shard has the owner-tagged columns, else the gather form when
   // every shard has cw4, else the wide records
-  bool sc = cp, ga = cp;
+  // nw: the narrow scatter form, at two or four tiles per wave when every shard has the pod word
+  // column (a batch with a shard that lacks it reads rec12 for all; KPE_LEAN6_SHAPE bit 6: never)
+  bool sc = cp, ga = cp, nw = cp && tpw >= 2 && !(dev->lean_shape & 64u);
   for (size_t k = 0; k < m; ++k) {
     const auto& D = *cs[k]->d;
     sc = sc && D.pack_ready && D.tag_ready, ga = ga && D.pack_ready && D.cw4_ready;
+    nw = nw && D.pw4_ready;
   }
   cp = sc || ga;
+  nw = nw && sc;
   uint32_t acc = 0, kt_max = 0;
   *bytes = 0;
   for (size_t k = 0; k < m; ++k) {
@@ -1439,7 +1450,7 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
     sh.rec = D.rec.as<uint32_t>(), sh.hdr = D.hdr.as<uint32_t>(), sh.crec = D.crec.as<uint32_t>();
     sh.vol = D.vol_src.as<uint32_t>(), sh.sys = D.sys_id.as<uint32_t>(), sh.pann = D.pann_kv.as<uint32_t>();
     sh.sann = D.c_sann.as<uint32_t>();
-    sh.rec12 = D.rec12.as<uint32_t>(), sh.cw4 = (sc ? D.tag : D.cw4).as<uint32_t>();
+    sh.rec12 = (nw ? D.pw4 : D.rec12).as<uint32_t>(), sh.cw4 = (sc ? D.tag : D.cw4).as<uint32_t>();
     sh.codes = D.psa_codes.as<uint8_t>();
     sh.kt = B.pimg.as<uint32_t>() + B.kt_lds;
     sh.verdicts = B.verdicts.as<uint8_t>();
@@ -1452,7 +1463,7 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
     acc += (uint32_t)((C.n + 256 * tpw - 1) / (256 * tpw));  // 4 waves x tpw tiles of 64 pods per block
     kt_max = std::max(kt_max, B.nkinds);
     a.need |= B.need;
-    *bytes += lean_bytes(C, D, B.need, R, masks, cp);
+    *bytes += lean_bytes(C, D, B.need, R, masks, cp, nw);
   }
   a.blk0[m] = acc;
   a.kt_words = (kt_max + 3u) & ~3u;
@@ -1467,8 +1478,9 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
   a.pod_tab = (cp ? dev->lean_pod_tab_c : dev->lean_pod_tab).as<uint32_t>();
   const size_t dyn = 4 * ((size_t)KPE_L6_PT_WORDS + a.kt_words + a.code_words + 4 * (size_t)a.wave_words);
   HIPCHK(kpe_launch_lean6(&a, dyn, lc ? 1 : 0, (a.need & NEED_SANN) || (dev->lean_shape & 1u) ? 1 : 0, cv ? 1 : 0,
-                         sc ? 2 : cp ? 1 : 0, s));
+                         nw ? 3 : sc ? 2 : cp ? 1 : 0, s));
   dev->lean_form = sc ? 2 : cp ? 1 : 0;
+  dev->lean_narrow = nw ? 1 : 0;
   return KPE_OK;
 }
 
@@ -1563,7 +1575,7 @@ kpe_status kpe_device_open(int ordinal, kpe_device** out) {
     const int t = atoi(ev);
     d->lean_tpw = t == 1 || t == 2 || t == 4 ? (uint32_t)t : 0u;
   }
-  if (const char* ev = getenv("KPE_LEAN6_SHAPE")) d->lean_shape = (uint32_t)atoi(ev) & 0x33u;
+  if (const char* ev = getenv("KPE_LEAN6_SHAPE")) d->lean_shape = (uint32_t)atoi(ev) & 0x73u;
   for (int k = 0; k < d->nlanes; ++k) {
     e = hipStreamCreateWithFlags(&d->lanes[k], hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -1668,6 +1680,9 @@ int kpe_debug_lean_kind(const kpe_corpus* c, uint64_t lim) {
 // wide records, 1 rec12 / cw4 (gather form), 2 the owner-tagged columns (scatter form); -1 before
 // the first launch.
 int kpe_debug_lean_form(const kpe_device* d) { return d ? d->lean_form : -KPE_E_INVALID; }
+// Diagnostic (not in kpe.h): 1 when that launch was the narrow scatter form, which reads the pod
+// word column pw4, not rec12; else 0.
+int kpe_debug_lean_narrow(const kpe_device* d) { return d ? d->lean_narrow : -KPE_E_INVALID; }
 
 kpe_status kpe_corpus_row_flags(const kpe_corpus* c, uint32_t* out) {
   if (!c || !out) return fail(KPE_E_INVALID, "kpe_corpus_row_flags: null argument");

@@ -235,7 +235,8 @@ __global__ void __launch_bounds__(256) kpe_psum_kernel(PsumArgs a) {
 }
 
 // ---- kpe_lean_pack_kernel: the compact columns of a corpus (once per corpus) --------------------
-// Thread i writes words {x, y, z} of pod record i and the container word of container record i
+// Thread i writes words {x, y, z} of pod record i, its pod word (kernels_abi.h kpe_l6_pack_pod;
+// a corpus of at most KPE_L6P_MAX_KINDS kinds) and the container word of container record i
 // (kernels_abi.h kpe_l6_pack_ctr): a re-packing of the uploaded records, launched where the
 // dictionary codes are (first podSecurity binding of the corpus, and a cold evaluation).
 __global__ void __launch_bounds__(256) kpe_lean_pack_kernel(LeanPackArgs a) {
@@ -244,6 +245,7 @@ __global__ void __launch_bounds__(256) kpe_lean_pack_kernel(LeanPackArgs a) {
     const uint4 r = reinterpret_cast<const uint4*>(a.rec)[i];
     uint32_t* const o = a.rec12 + 3u * (size_t)i;
     o[0] = r.x, o[1] = r.y, o[2] = r.z;
+    if (a.pw4) a.pw4[i] = kpe_l6_pack_pod(r.x, r.y);
   }
   if (a.cw4 && i < a.nctr) {
     const uint2 e = reinterpret_cast<const uint2*>(a.crec)[i];
@@ -671,7 +673,12 @@ __device__ __forceinline__ void l6_gather_tiles() {
 // restated here and to be kept in step with it: as shared __forceinline__ helpers they cost the
 // C2 instantiations scalar spills at eight blocks per CU (gather 9 -> 20-25, scatter 0 -> 8-14;
 // DESIGN.md section 9).
-template <int T, bool SANN>
+// NW (T >= 2: the launches of at least 32,768 tiles, the bandwidth-bound ones): the narrow form.
+// The pod record is the corpus's one-word column pw4 (kernels_abi.h kpe_l6_pack_pod;
+// LeanShard::rec12 is its base), one dword load per tile at a 4-byte stride, 256 contiguous bytes
+// per wave; 8 bytes per pod less than words x and y at rec12's 12-byte stride, whose cache lines
+// arrive whole. The T = 1 launches keep rec12.
+template <int T, bool SANN, bool NW>
 __device__ __forceinline__ void l6_scatter_tiles() {
   extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
   CBArgs& a = *(CBArgs*)kargs();
@@ -689,7 +696,7 @@ __device__ __forceinline__ void l6_scatter_tiles() {
   const uint32_t tile0 = ((gb - a.blk0[lo]) * 4u + wv) * (uint32_t)T;
   const uint32_t need = a.need;
   const bool nvol = need & NEED_VOL, nsys = need & NEED_SYS, npann = need & NEED_PANN;
-  const Rsrc REC = make_rsrc(S.rec12, n * 12u);
+  const Rsrc REC = make_rsrc(S.rec12, NW ? n * 4u : n * 12u);
   const Rsrc HDR = make_rsrc(S.hdr, (ntiles + 1u) * 16u);
   // every load of the tagged columns lies inside the allocation (slack included): what a slot
   // past a tile's count holds is dropped by the count, not by the descriptor
@@ -699,11 +706,15 @@ __device__ __forceinline__ void l6_scatter_tiles() {
   const Rsrc SAN = make_rsrc(S.sann, SANN && (need & NEED_SANN) ? S.nctr * 4u : 0u);
   const uint32_t l4 = lane * 4u;
   auto ldt = [&](uint32_t voff, uint32_t soff) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(TAG, voff, soff, 0); };
-  // ---- step 1: headers and records (words x and y; the packed counts are not read)
+  // ---- step 1: headers and records (words x and y, or NW: the pod word; the packed counts are
+  // not read)
   const uint32_t hall = bload1(HDR, (tile0 * 4u + min(lane, 4u * T + 3u)) * 4u);
-  uint2 rec[T];
+  typename std::conditional<NW, uint32_t, uint2>::type rec[T];
 #pragma unroll
-  for (int j = 0; j < T; ++j) rec[j] = bload2(REC, ((tile0 + j) * 64u + lane) * 12u);  // past n: zeros
+  for (int j = 0; j < T; ++j) {  // past n: zeros
+    if constexpr (NW) rec[j] = bload1(REC, ((tile0 + j) * 64u + lane) * 4u);
+    else rec[j] = bload2(REC, ((tile0 + j) * 64u + lane) * 12u);
+  }
   const uint32_t nk = S.nkinds;
   const uint32_t k0 = t < nk ? S.kt[t] : 0u;
   const uint32_t ncw = (S.L.bytes + 3u) >> 2;
@@ -848,9 +859,17 @@ __device__ __forceinline__ void l6_scatter_tiles() {
     __builtin_amdgcn_wave_barrier();
     const uint32_t cw = acc[lane];
     // ---- the version classes, the rule match (kind table) and the verdict bytes: as the gather form
-    const uint32_t pw = rec[j].x;
-    uint32_t failr = 0;
-    const uint32_t tw = kpe_l6_pod_lookup(dyn, pw);
+    uint32_t failr = 0, tw, cls, kind;
+    bool derr;
+    if constexpr (NW) {
+      const uint32_t w = rec[j];
+      tw = kpe_l6p_pod_lookup(dyn, w), cls = kpe_l6p_class(w), kind = kpe_l6p_kind(w);
+      derr = w & KPE_L6P_DECODE_ERR;
+    } else {
+      const uint32_t pw = rec[j].x;
+      tw = kpe_l6_pod_lookup(dyn, pw), cls = (pw >> PR_CLASS_SH) & R_CLASS_MASK, kind = GVK_KIND(rec[j].y);
+      derr = pw & PR_DECODE_ERR;
+    }
     const uint32_t ev = kpe_l6c_pod_split(cw, tw, 0u);
     const uint32_t ev_nw = ev & (uint32_t)((int32_t)tw >> 31);  // KPE_L6_PT_NW over the word
 #pragma unroll
@@ -861,9 +880,7 @@ __device__ __forceinline__ void l6_scatter_tiles() {
       asm("" : "+v"(m));  // keeps the select on inline constants (see the gather form)
       failr |= m & crm[c];
     }
-    const uint32_t cls = (pw >> PR_CLASS_SH) & R_CLASS_MASK;
-    const bool err = cls == R_CLASS_OTHER || (pw & PR_DECODE_ERR);
-    const uint32_t kind = GVK_KIND(rec[j].y);
+    const bool err = cls == R_CLASS_OTHER || derr;
     const uint32_t matched = live && kind < nk ? kt[kind] : 0u;
     const uint32_t E = matched & ((err ? pss_rules : 0u) | ep_rules);
     const uint32_t F = (matched & pss_rules & failr & ~E) | (matched & pat_rules);  // F|E = PENDING
@@ -899,11 +916,13 @@ __device__ __forceinline__ void l6_scatter_tiles() {
 
 // SC: the scatter form of CP over the corpus's owner-tagged columns (l6_scatter_tiles); each
 // instantiation holds the one body it runs.
-template <int T, bool LC, bool SANN, bool CV, bool CP = false, bool SC = false>
+// NW: its narrow form, over the pod word column (T >= 2).
+template <int T, bool LC, bool SANN, bool CV, bool CP = false, bool SC = false, bool NW = false>
 __global__ void __launch_bounds__(kLB, l6_waves(SANN, CP)) __attribute__((amdgpu_num_sgpr(KPE_LEAN6_SGPRS)))
 kpe_lean6_kernel(LeanBatchArgs) {
   static_assert(!(CP && CV), "the compact columns are read by the verdict-only form");
   static_assert(!SC || (CP && LC), "the scatter form is a compact form with the code bytes in LDS");
-  if constexpr (SC) l6_scatter_tiles<T, SANN>();
+  static_assert(!NW || (SC && T >= 2), "the narrow form is a scatter form of two or four tiles per wave");
+  if constexpr (SC) l6_scatter_tiles<T, SANN, NW>();
   else l6_gather_tiles<T, LC, SANN, CV, CP>();
 }

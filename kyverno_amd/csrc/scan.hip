@@ -1256,12 +1256,20 @@ extern "C" hipError_t kpe_launch_selmask(const SelMaskArgs* a, hipStream_t s) {
 // one instantiation that covers every program runs.
 // cp: the verdict-only form reads the compact columns (LeanShard::rec12 / cw4; class masks and pod
 // table in the packed numbering); kpe_lean6_compact says which launches may ask for it. cp == 2:
-// the scatter form over the owner-tagged columns (SC; LeanShard::cw4 is their base).
+// the scatter form over the owner-tagged columns (SC; LeanShard::cw4 is their base). cp == 3
+// (tpw 2 or 4 only): its narrow form (NW; LeanShard::rec12 is the pod word column pw4).
 template <int T, bool LC>
 static void lean6_go(int sann, int cv, int cp, dim3 g, dim3 b, size_t dyn_bytes, hipStream_t s, const LeanBatchArgs& a) {
   if constexpr (!LC) {
     hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, true>), g, b, dyn_bytes, s, a);
   } else {
+    if constexpr (T >= 2) {
+      if (cp == 3) {
+        if (sann) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, false, true, true, true>), g, b, dyn_bytes, s, a);
+        else hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, false, false, true, true, true>), g, b, dyn_bytes, s, a);
+        return;
+      }
+    }
     if (cp == 2 && sann) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, false, true, true>), g, b, dyn_bytes, s, a);
     else if (cp == 2) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, false, false, true, true>), g, b, dyn_bytes, s, a);
     else if (sann && cv) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, true>), g, b, dyn_bytes, s, a);
@@ -1279,6 +1287,7 @@ extern "C" hipError_t kpe_launch_lean6(const LeanBatchArgs* a, size_t dyn_bytes,
   if (a->nshards == 0 || grid == 0) return hipSuccess;
   if (!cv && a->ncls > KPE_L6_CLS) return hipErrorInvalidValue;
   if (cp && !kpe_lean6_compact(lc, cv)) return hipErrorInvalidValue;
+  if (cp == 3 && a->tpw < 2) return hipErrorInvalidValue;
   const dim3 g(grid), b(kLB);
   if (a->tpw == 4 && lc) lean6_go<4, true>(sann, cv, cp, g, b, dyn_bytes, s, *a);
   else if (a->tpw == 2 && lc) lean6_go<2, true>(sann, cv, cp, g, b, dyn_bytes, s, *a);
