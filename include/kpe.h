@@ -175,10 +175,32 @@ const char* kpe_corpus_namespace(const kpe_corpus* c, int64_t g);
 /* out[i] = the group of row i, for each of the kpe_corpus_num_resources rows. */
 kpe_status kpe_corpus_row_namespaces(const kpe_corpus* c, uint32_t* out);
 /* out[g] = the rows of group g (G entries; their sum is N). The KPE_NA cells of a (group, rule)
- * are these rows minus the six counters of kpe_ns_counts. */
+ * are these rows minus the six counters of kpe_ns_counts. Retired rows (kpe_corpus_retire_rows)
+ * are still counted here: every cell of theirs is KPE_NA, so the statement holds for them too. */
 kpe_status kpe_corpus_namespace_rows(const kpe_corpus* c, uint64_t* out);
 /* Copy the columns to device memory (HBM). Evaluation requires this. */
 kpe_status kpe_corpus_upload(kpe_device* dev, kpe_corpus* c);
+/* Retire rows of a corpus (a resource that was deleted, or replaced by a row of another corpus):
+ * from the next evaluation on, every cell of a retired row is KPE_NA and every check-mask word of
+ * it 0, in every form of evaluation (kpe_evaluate, kpe_evaluate_async[_ex], kpe_evaluate_batch_async
+ * and its multi-shard launches, kpe_evaluate_sharded; with and without KPE_EVAL_MASKS /
+ * KPE_EVAL_COLD), before any consumer reads: the fetches, counts, selections, summaries, namespace
+ * counts, kept results and deltas, fingerprints (0, "no report", for a retired row), report rows,
+ * packed and device verdicts and the traces all see a row without responses. Retirement overrides
+ * whatever the row would otherwise be (KPE_UNDECIDED of a row past a limit or with a context error,
+ * a decode-error KPE_ERROR, an applyRules: One outcome). Results of an evaluation that was already
+ * enqueued, and kept results, stay as they are.
+ * The set only grows (union; duplicates and any order allowed), belongs to the corpus until
+ * kpe_corpus_free and survives kpe_corpus_upload, which sends it again. dev may be NULL for a corpus
+ * that is not uploaded: the set is recorded on the host and travels with the next upload. For an
+ * uploaded corpus the device list is refreshed on the corpus's stream, ordered before its next
+ * evaluation. KPE_E_INVALID for a row >= N or a null rows with n > 0; KPE_E_STATE for an uploaded
+ * corpus with a null device or a device other than its own; both checked before any device call,
+ * and the set is then left untouched. */
+kpe_status kpe_corpus_retire_rows(kpe_device* dev, kpe_corpus* c, const uint64_t* rows, uint64_t n);
+/* The retired rows, ascending and unique: the first min(total, cap) into rows[]; returns the total
+ * (rows == NULL with cap == 0 counts only), or -kpe_status. Host only. */
+int64_t kpe_corpus_retired_rows(const kpe_corpus* c, uint64_t* rows, uint64_t cap);
 /* The corpus's per-pod PSA summary, built on dev (waits for it; builds it first when no LEAN
  * evaluation has yet): 2 words per row (include-free layout of kyverno_amd/csrc/schema.h PS_*:
  * x = OR of the pod's container state bitmaps, y = the list codes under the PSA library's fixed
@@ -327,6 +349,21 @@ kpe_status kpe_delta_column_map(const kpe_corpus* c, const kpe_program* prog, in
 #define KPE_DELTA_MAX_RULES 4096
 int64_t kpe_changed_rows(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const int32_t* old_of,
                          const uint8_t* always, uint64_t* rows, uint8_t* verdict_rows, uint64_t cap);
+/* The comparison across corpora, for the rows a small delta corpus replaces in a resident one.
+ * pairs: npairs x {new_row, old_row}. Pair k compares row new_row of the last evaluation of prog on
+ * c_new with row old_row of c_old's KEPT matrix, by the rules of kpe_changed_rows (old_of, always,
+ * disappeared columns; old_of == NULL maps by rule name against c_old's kept names, as
+ * kpe_delta_column_map does). Writes the first min(total, cap) indices k of the changed pairs,
+ * ascending, into changed[] and, when verdict_rows is not NULL, their rows of the new matrix (Rn
+ * bytes each); memory past that is not written. changed == NULL with cap == 0 counts only. An old_row
+ * may occur in several pairs; c_new == c_old is allowed. Returns the total, or -kpe_status:
+ * KPE_E_INVALID for a null argument (pairs with npairs > 0), cap > 0 without changed, a pair's row
+ * outside its corpus, or a bad column map; KPE_E_LIMIT past KPE_DELTA_MAX_RULES; all checked before
+ * any device call. KPE_E_STATE when c_old keeps nothing, c_new has no evaluation of prog, or either
+ * corpus is not uploaded to dev. The host form is kpe_changed_rows_host over the gathered rows. */
+int64_t kpe_changed_pairs(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c_new, const kpe_corpus* c_old,
+                          const uint64_t* pairs, uint64_t npairs, const int32_t* old_of, const uint8_t* always,
+                          uint64_t* changed, uint8_t* verdict_rows, uint64_t cap);
 /* What a policy edit does to the cluster: per new column r the table out[r * 64 + old * 8 + new] of
  * rows by kept and new verdict code (old = KPE_NA for an unmapped column); a column's table sums to
  * N. out: Rn x 64 counters. Arguments, map and errors as kpe_changed_rows. */
@@ -416,6 +453,17 @@ int kpe_fingerprints_kept(const kpe_corpus* c); /* 0 or 1 */
 int64_t kpe_changed_rows_fp(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint64_t* salts,
                             const uint64_t* msg_salts, uint8_t msg_codes, uint32_t flags, uint64_t* rows,
                             uint8_t* verdict_rows, uint64_t* fps_out, uint64_t cap);
+/* The fingerprint form of kpe_changed_pairs: the fingerprint of row new_row of the last evaluation of
+ * prog on c_new under (salts, msg_salts, msg_codes, flags) against c_old's KEPT fingerprint of
+ * old_row. Writes the changed pairs' indices, their rows of the new matrix and their new
+ * fingerprints (fps_out, may be NULL), with kpe_changed_rows_fp's cap and error conventions;
+ * KPE_E_INVALID also for a pair's row outside its corpus, KPE_E_STATE when c_old keeps no
+ * fingerprints or either corpus is not uploaded to dev. The host form is kpe_row_fingerprints_host
+ * over the gathered rows against kpe_fingerprints_fetch. */
+int64_t kpe_changed_pairs_fp(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c_new, const kpe_corpus* c_old,
+                             const uint64_t* pairs, uint64_t npairs, const uint64_t* salts, const uint64_t* msg_salts,
+                             uint8_t msg_codes, uint32_t flags, uint64_t* changed, uint8_t* verdict_rows,
+                             uint64_t* fps_out, uint64_t cap);
 /* The host twin of the comparison: the indices i < n with old_fp[i] != new_fp[i], same cap / count-only /
  * return conventions. Host only. */
 int64_t kpe_changed_fingerprints_host(const uint64_t* old_fp, const uint64_t* new_fp, uint64_t n, uint64_t* rows,

@@ -127,6 +127,14 @@ def load():
     L.kpe_fingerprints_kept.restype = ctypes.c_int
     L.kpe_changed_rows_fp.argtypes = [vp, vp, vp, vp, vp, u8, u32, vp, vp, vp, u64]
     L.kpe_changed_rows_fp.restype = i64
+    L.kpe_corpus_retire_rows.argtypes = [vp, vp, vp, u64]
+    L.kpe_corpus_retire_rows.restype = ctypes.c_int
+    L.kpe_corpus_retired_rows.argtypes = [vp, vp, u64]
+    L.kpe_corpus_retired_rows.restype = i64
+    L.kpe_changed_pairs.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64]
+    L.kpe_changed_pairs.restype = i64
+    L.kpe_changed_pairs_fp.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, u8, u32, vp, vp, vp, u64]
+    L.kpe_changed_pairs_fp.restype = i64
     L.kpe_changed_fingerprints_host.argtypes = [vp, vp, u64, vp, u64]
     L.kpe_changed_fingerprints_host.restype = i64
     L.kpe_corpus_num_namespaces.argtypes = [vp]

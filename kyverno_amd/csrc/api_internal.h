@@ -29,6 +29,9 @@ struct kpe_corpus {
   std::unique_ptr<kpe::DeviceCorpus> d;
   mutable std::mutex ns_mu;
   mutable std::unique_ptr<NsGroups> ns;  // built on first use
+  // the retired rows (kpe_corpus_retire_rows), ascending and unique; the set only grows and lives
+  // with the handle. The device copy is DeviceCorpus::retired (every upload sends it again).
+  std::vector<uint32_t> retired;
   ~kpe_corpus();  // kpe_api.cpp, where kpe::DeviceCorpus is complete
 };
 
@@ -283,6 +286,7 @@ struct DeviceCorpus {
   DevBuf doc, doc_off, img_off, scal, scal_text;  // document tape + scalar table (pattern rules)
   DevBuf doc_perm;  // rows by descending tape size: the pattern / condition kernels' lane -> row map
   DevBuf limit_rows;                     // rows past a per-resource limit
+  DevBuf retired;                        // kpe_corpus::retired (kpe_retire_rows_kernel reads it last)
   // cold pod columns, uploaded on the first binding of a program with podSecurity exclusions
   DevBuf ctr_off, vol_off, sys_off, pann_off, c_name, c_image, c_sann_key, c_sec_str, c_pm_str, c_selt_str, c_selu_str,
       c_selr_str, cport_off, cport_str, pann_k, pann_v, p_cold;

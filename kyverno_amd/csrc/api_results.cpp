@@ -371,6 +371,118 @@ int64_t kpe_changed_rows(kpe_device* dev, const kpe_program* prog, const kpe_cor
   return st ? -(int64_t)st : (int64_t)total;
 }
 
+// What kpe_changed_pairs and kpe_changed_pairs_fp check of their pair list before any device call.
+static kpe_status pairs_args(const kpe_device* dev, const kpe_program* prog, const kpe_corpus* c_new,
+                             const kpe_corpus* c_old, const uint64_t* pairs, uint64_t npairs, const uint64_t* changed,
+                             uint64_t cap) {
+  if (!dev || !prog || !c_new || !c_old || (npairs && !pairs)) return fail(KPE_E_INVALID, "null argument");
+  if (cap && !changed) return fail(KPE_E_INVALID, "cap > 0 without a changed buffer");
+  const uint64_t nn = (uint64_t)c_new->c->n, no = (uint64_t)c_old->c->n;
+  for (uint64_t k = 0; k < npairs; ++k)
+    if (pairs[2 * k] >= nn || pairs[2 * k + 1] >= no) return fail(KPE_E_INVALID, "pair row past its corpus");
+  return KPE_OK;
+}
+// Their state checks (under dev->mu), and the stream of the comparison: the one of c_new's last
+// evaluation, after c_old's pending work (its keep is enqueued on its own stream).
+static kpe_status pairs_bound(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c_new, const kpe_corpus* c_old,
+                              hipStream_t* s) {
+  if (!c_new->d) return fail(KPE_E_STATE, "corpus not uploaded");
+  if (kpe_status st = delta_bound(dev, prog, c_new)) return st;
+  if (c_old->d->ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  *s = c_new->d->bind.last ? c_new->d->bind.last : dev->stream;
+  const hipStream_t so = c_old->d->bind.last;
+  if (so && so != *s) HIPCHK(hipStreamSynchronize(so));
+  return KPE_OK;
+}
+// The carve of a pair call's scratch: the pairs, their flag bytes as an npairs x 1 matrix for the
+// selection chain, its tile offsets and counts and its one mask, then `extra` bytes (16-byte aligned).
+struct PairScratch {
+  uint64_t ntiles;
+  uint64_t* d_pairs;
+  uint8_t* d_flags;
+  uint64_t* d_off;
+  uint32_t* d_cnt;
+  uint8_t* d_sel;
+  uint8_t* d_extra;
+};
+static kpe_status pairs_scratch(DevBuf& scratch, const uint64_t* pairs, uint64_t npairs, size_t extra, hipStream_t s,
+                                PairScratch* o) {
+  o->ntiles = (npairs + 4095u) / 4096u;
+  const size_t pair_bytes = (size_t)npairs * 16;
+  const size_t flag_bytes = (size_t)((npairs + 15u) & ~(uint64_t)15u);
+  const size_t off_bytes = (size_t)((o->ntiles + 2) & ~(uint64_t)1) * 8;
+  const size_t cnt_bytes = (size_t)((o->ntiles + 3) & ~(uint64_t)3) * 4;
+  HIPCHK(scratch.ensure(pair_bytes + flag_bytes + off_bytes + cnt_bytes + 16 + extra));
+  uint8_t* base = scratch.as<uint8_t>();
+  o->d_pairs = reinterpret_cast<uint64_t*>(base);
+  o->d_flags = base + pair_bytes;
+  o->d_off = reinterpret_cast<uint64_t*>(base + pair_bytes + flag_bytes);
+  o->d_cnt = reinterpret_cast<uint32_t*>(base + pair_bytes + flag_bytes + off_bytes);
+  o->d_sel = base + pair_bytes + flag_bytes + off_bytes + cnt_bytes;
+  o->d_extra = o->d_sel + 16;
+  static const uint8_t sel1 = (uint8_t)KPE_SEL(1);
+  HIPCHK(hipMemcpyAsync(o->d_pairs, pairs, pair_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(o->d_sel, &sel1, 1, hipMemcpyHostToDevice, s));
+  return KPE_OK;
+}
+
+static kpe_status changed_pairs_impl(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c_new,
+                                     const kpe_corpus* c_old, const uint64_t* pairs, uint64_t npairs,
+                                     const int32_t* old_of, const uint8_t* always, uint64_t* changed_out,
+                                     uint8_t* vrows_out, uint64_t cap, uint64_t* total_out) {
+  *total_out = 0;
+  if (kpe_status st = pairs_args(dev, prog, c_new, c_old, pairs, npairs, changed_out, cap)) return st;
+  std::vector<uint32_t> tab;
+  std::vector<uint8_t> unm;
+  bool any_unm = false;
+  if (kpe_status st = delta_tables(prog, c_old, old_of, always, tab, unm, &any_unm)) return st;
+  const size_t Rn = tab.size(), Ro = unm.size();
+  std::lock_guard<std::mutex> lk(dev->mu);
+  hipStream_t s = nullptr;
+  if (kpe_status st = pairs_bound(dev, prog, c_new, c_old, &s)) return st;
+  if (!npairs) return KPE_OK;
+  const uint8_t* vnew = c_new->d->bind.verdicts.as<uint8_t>();
+  const size_t tab_bytes = (Rn * 4 + 15u) & ~(size_t)15u;
+  DevBuf scratch, didx, drows, dverd;  // this call's, freed on every return path
+  PairScratch S;
+  if (kpe_status st = pairs_scratch(scratch, pairs, npairs, tab_bytes + Ro, s, &S)) return st;
+  uint32_t* d_tab = reinterpret_cast<uint32_t*>(S.d_extra);
+  uint8_t* d_unm = S.d_extra + tab_bytes;
+  if (Rn) HIPCHK(hipMemcpyAsync(d_tab, tab.data(), Rn * 4, hipMemcpyHostToDevice, s));
+  if (any_unm) HIPCHK(hipMemcpyAsync(d_unm, unm.data(), Ro, hipMemcpyHostToDevice, s));
+  HIPCHK(kpe_launch_delta_pairs(vnew, c_old->d->kept.as<uint8_t>(), S.d_pairs, npairs, (uint32_t)Rn, (uint32_t)Ro, d_tab,
+                                any_unm ? d_unm : nullptr, S.d_flags, s));
+  HIPCHK(kpe_launch_select_count(S.d_flags, npairs, 1u, S.d_sel, 0, S.d_cnt, S.d_off, s));
+  uint64_t total = 0;
+  HIPCHK(hipMemcpyAsync(&total, S.d_off + S.ntiles, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));  // also: pairs and the tables are copied
+  *total_out = total;
+  const uint64_t m = std::min(total, cap);
+  if (!m) return KPE_OK;
+  HIPCHK(didx.ensure((size_t)m * 8));
+  HIPCHK(kpe_launch_select_scatter(S.d_flags, npairs, 1u, S.d_sel, 0, S.d_off, m, didx.as<uint64_t>(), nullptr, s));
+  const bool vr = vrows_out && Rn;
+  if (vr) {
+    HIPCHK(drows.ensure((size_t)m * 8));
+    HIPCHK(dverd.ensure((size_t)m * Rn));
+    HIPCHK(kpe_launch_pair_rows(S.d_pairs, didx.as<uint64_t>(), m, drows.as<uint64_t>(), s));
+    HIPCHK(kpe_launch_gather_rows(vnew, (uint32_t)Rn, drows.as<uint64_t>(), m, dverd.as<uint8_t>(), s));
+  }
+  HIPCHK(hipMemcpyAsync(changed_out, didx.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+  if (vr) HIPCHK(hipMemcpyAsync(vrows_out, dverd.p, (size_t)m * Rn, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return KPE_OK;
+}
+
+int64_t kpe_changed_pairs(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c_new, const kpe_corpus* c_old,
+                          const uint64_t* pairs, uint64_t npairs, const int32_t* old_of, const uint8_t* always,
+                          uint64_t* changed, uint8_t* verdict_rows, uint64_t cap) {
+  uint64_t total = 0;
+  const kpe_status st =
+      changed_pairs_impl(dev, prog, c_new, c_old, pairs, npairs, old_of, always, changed, verdict_rows, cap, &total);
+  return st ? -(int64_t)st : (int64_t)total;
+}
+
 kpe_status kpe_delta_transitions(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const int32_t* old_of,
                                  uint64_t* out) {
   if (!dev || !prog || !c) return fail(KPE_E_INVALID, "null argument");
@@ -672,6 +784,71 @@ int64_t kpe_changed_rows_fp(kpe_device* dev, const kpe_program* prog, const kpe_
   uint64_t total = 0;
   const kpe_status st =
       changed_fp_impl(dev, prog, c, salts, msg_salts, msg_codes, flags, rows, verdict_rows, fps_out, cap, &total);
+  return st ? -(int64_t)st : (int64_t)total;
+}
+
+static kpe_status changed_pairs_fp_impl(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c_new,
+                                        const kpe_corpus* c_old, const uint64_t* pairs, uint64_t npairs,
+                                        const uint64_t* salts, const uint64_t* msg_salts, uint8_t msg_codes, uint32_t flags,
+                                        uint64_t* changed_out, uint8_t* vrows_out, uint64_t* fps_out, uint64_t cap,
+                                        uint64_t* total_out) {
+  *total_out = 0;
+  if (kpe_status st = pairs_args(dev, prog, c_new, c_old, pairs, npairs, changed_out, cap)) return st;
+  std::vector<uint64_t> tbl;
+  if (kpe_status st = fp_table(prog, salts, msg_salts, flags, tbl)) return st;
+  if (!c_old->d || !c_old->d->fps_kept) return fail(KPE_E_STATE, "no kept fingerprints on this corpus");
+  const size_t R = tbl.size() / 2;
+  std::lock_guard<std::mutex> lk(dev->mu);
+  if (!c_new->d) return fail(KPE_E_STATE, "corpus not uploaded");
+  if (kpe_status st = fp_bound(dev, prog, c_new, flags)) return st;
+  hipStream_t s = nullptr;
+  if (kpe_status st = pairs_bound(dev, prog, c_new, c_old, &s)) return st;
+  if (!npairs) return KPE_OK;
+  auto& B = c_new->d->bind;
+  const size_t fp_bytes = (size_t)((npairs + 1u) & ~(uint64_t)1u) * 8;
+  DevBuf scratch, didx, drows, dverd, dfps;  // this call's, freed on every return path
+  PairScratch S;
+  if (kpe_status st = pairs_scratch(scratch, pairs, npairs, fp_bytes + R * 16, s, &S)) return st;
+  uint64_t* d_new = reinterpret_cast<uint64_t*>(S.d_extra);
+  uint64_t* d_tbl = d_new + fp_bytes / 8;
+  if (R) HIPCHK(hipMemcpyAsync(d_tbl, tbl.data(), R * 16, hipMemcpyHostToDevice, s));
+  HIPCHK(kpe_launch_fp_pairs(B.verdicts.as<uint8_t>(), (flags & KPE_FP_MASKS) ? B.masks.as<uint32_t>() : nullptr,
+                             (uint32_t)R, S.d_pairs, npairs, d_tbl, msg_codes, c_old->d->fps.as<uint64_t>(), d_new,
+                             S.d_flags, s));
+  HIPCHK(kpe_launch_select_count(S.d_flags, npairs, 1u, S.d_sel, 0, S.d_cnt, S.d_off, s));
+  uint64_t total = 0;
+  HIPCHK(hipMemcpyAsync(&total, S.d_off + S.ntiles, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));  // also: pairs and the table are copied
+  *total_out = total;
+  const uint64_t m = std::min(total, cap);
+  if (!m) return KPE_OK;
+  HIPCHK(didx.ensure((size_t)m * 8));
+  HIPCHK(kpe_launch_select_scatter(S.d_flags, npairs, 1u, S.d_sel, 0, S.d_off, m, didx.as<uint64_t>(), nullptr, s));
+  const bool vr = vrows_out && R;
+  if (vr) {
+    HIPCHK(drows.ensure((size_t)m * 8));
+    HIPCHK(dverd.ensure((size_t)m * R));
+    HIPCHK(kpe_launch_pair_rows(S.d_pairs, didx.as<uint64_t>(), m, drows.as<uint64_t>(), s));
+    HIPCHK(kpe_launch_gather_rows(B.verdicts.as<uint8_t>(), (uint32_t)R, drows.as<uint64_t>(), m, dverd.as<uint8_t>(), s));
+  }
+  if (fps_out) {
+    HIPCHK(dfps.ensure((size_t)m * 8));
+    HIPCHK(kpe_launch_fp_gather(d_new, didx.as<uint64_t>(), m, dfps.as<uint64_t>(), s));
+  }
+  HIPCHK(hipMemcpyAsync(changed_out, didx.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+  if (vr) HIPCHK(hipMemcpyAsync(vrows_out, dverd.p, (size_t)m * R, hipMemcpyDeviceToHost, s));
+  if (fps_out) HIPCHK(hipMemcpyAsync(fps_out, dfps.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return KPE_OK;
+}
+
+int64_t kpe_changed_pairs_fp(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c_new, const kpe_corpus* c_old,
+                             const uint64_t* pairs, uint64_t npairs, const uint64_t* salts, const uint64_t* msg_salts,
+                             uint8_t msg_codes, uint32_t flags, uint64_t* changed, uint8_t* verdict_rows,
+                             uint64_t* fps_out, uint64_t cap) {
+  uint64_t total = 0;
+  const kpe_status st = changed_pairs_fp_impl(dev, prog, c_new, c_old, pairs, npairs, salts, msg_salts, msg_codes, flags,
+                                              changed, verdict_rows, fps_out, cap, &total);
   return st ? -(int64_t)st : (int64_t)total;
 }
 

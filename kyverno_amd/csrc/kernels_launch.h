@@ -56,6 +56,10 @@ hipError_t kpe_launch_fill_rows(uint8_t* verdicts, uint32_t R, const uint32_t* r
                                 hipStream_t s);
 hipError_t kpe_launch_apply_one(uint8_t* verdicts, uint32_t* masks, int64_t n, uint32_t R, const uint32_t* segs,
                                 uint32_t nsegs, hipStream_t s);
+// retired rows (kpe_corpus_retire_rows): the listed rows' R verdict bytes to KPE_NA and, when masks is
+// not NULL, their R mask words to 0. verdicts is 4-byte aligned; rows < N, any order.
+hipError_t kpe_launch_retire_rows(uint8_t* verdicts, uint32_t* masks, uint32_t R, const uint32_t* rows, uint32_t nrows,
+                                  hipStream_t s);
 hipError_t kpe_launch_pack3(const uint8_t* v, uint64_t cells, uint32_t* out, hipStream_t s);
 hipError_t kpe_launch_select_count(const uint8_t* v, uint64_t cells, uint32_t R, const uint8_t* sel, int na_selected,
                                    uint32_t* tile_counts, uint64_t* tile_offs, hipStream_t s);
@@ -80,6 +84,13 @@ hipError_t kpe_launch_gather_rows(const uint8_t* v, uint32_t R, const uint64_t* 
 hipError_t kpe_launch_delta_transitions(const uint8_t* vnew, const uint8_t* vold, uint64_t n, uint32_t Rn, uint32_t Ro,
                                         const uint32_t* tab, unsigned long long* out, hipStream_t s);
 uint32_t kpe_delta_max_rules(void);
+// result deltas across corpora (kpe_changed_pairs). pairs: npairs x {row of vnew, row of vold};
+// tab / unmapped as above; flags: npairs bytes, one per pair, each written once.
+hipError_t kpe_launch_delta_pairs(const uint8_t* vnew, const uint8_t* vold, const uint64_t* pairs, uint64_t npairs,
+                                  uint32_t Rn, uint32_t Ro, const uint32_t* tab, const uint8_t* unmapped, uint8_t* flags,
+                                  hipStream_t s);
+// out[i] = pairs[2 * idx[i]] (the new row of pair idx[i]), m words
+hipError_t kpe_launch_pair_rows(const uint64_t* pairs, const uint64_t* idx, uint64_t m, uint64_t* out, hipStream_t s);
 
 // row fingerprints (kpe_fetch_row_fingerprints, kpe_fingerprints_keep, kpe_changed_rows_fp). tbl:
 // 2 R words, [salts][msg_salts]; masks: the N x R cv mask words, or NULL when they do not count;
@@ -90,6 +101,11 @@ hipError_t kpe_launch_row_fp(const uint8_t* v, const uint32_t* masks, uint32_t R
 hipError_t kpe_launch_fp_diff(const uint64_t* a, const uint64_t* b, uint64_t n, uint8_t* flags, hipStream_t s);
 // out[i] = fp[rows[i]], m words
 hipError_t kpe_launch_fp_gather(const uint64_t* fp, const uint64_t* rows, uint64_t m, uint64_t* out, hipStream_t s);
+// the fingerprint form over a pair list (kpe_changed_pairs_fp): fp_out[k] = the fingerprint of row
+// pairs[2 k] of v, flags[k] = it differs from kept[pairs[2 k + 1]]. R <= kpe_delta_max_rules() (0 allowed).
+hipError_t kpe_launch_fp_pairs(const uint8_t* v, const uint32_t* masks, uint32_t R, const uint64_t* pairs, uint64_t npairs,
+                               const uint64_t* tbl, uint32_t msg_codes, const uint64_t* kept, uint64_t* fp_out,
+                               uint8_t* flags, hipStream_t s);
 
 // report detail of a row list (kpe_fetch_report_rows) over the compact matrix v of `cells` cells
 // (a multiple of R). need: 3 R bytes, [mask][cond][pattern] in the KPE_SEL convention, bit 0

@@ -1031,6 +1031,17 @@ kpe_status ensure_binding(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc
 kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::DeviceProgram& PD, kpe_corpus* const* cs,
                         size_t m, bool masks, hipStream_t s, double* bytes);
 
+// The last pass of an evaluation of a corpus with retired rows (kpe_corpus_retire_rows): their
+// cells KPE_NA, their mask words 0 when this evaluation wrote masks. Nothing is launched for a
+// corpus without retired rows.
+kpe_status retire_pass(kpe_corpus* cc, uint32_t R, bool masks, hipStream_t s) {
+  if (cc->retired.empty()) return KPE_OK;
+  auto& D = *cc->d;
+  HIPCHK(kpe_launch_retire_rows(D.bind.verdicts.as<uint8_t>(), masks ? D.bind.masks.as<uint32_t>() : nullptr, R,
+                                D.retired.as<uint32_t>(), (uint32_t)cc->retired.size(), s));
+  return KPE_OK;
+}
+
 kpe_status launch(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc, bool masks, bool cold = false) {
   auto& P = *pp->p;
   auto& C = *cc->c;
@@ -1388,9 +1399,11 @@ kpe_status launch(kpe_device* dev, const kpe_program* pp, kpe_corpus* cc, bool m
   if (!C.limit_rows.empty())  // last: no later kernel may resolve these cells
     HIPCHK(kpe_launch_fill_rows(B.verdicts.as<uint8_t>(), (uint32_t)R, D.limit_rows.as<uint32_t>(),
                                 (uint32_t)C.limit_rows.size(), KPE_UNDECIDED_, s));
+  if (kpe_status st = retire_pass(cc, (uint32_t)R, masks, s)) return st;  // after everything: these rows give no response
   if (dev->timing) {
     HIPCHK(hipEventRecord(ev.d, s));
-    ev.post = !P.cond.rules.empty() || !P.pssx.rules.empty() || !P.pat.rules.empty() || B.napply_segs || !C.limit_rows.empty();
+    ev.post = !P.cond.rules.empty() || !P.pssx.rules.empty() || !P.pat.rules.empty() || B.napply_segs ||
+              !C.limit_rows.empty() || !cc->retired.empty();
     const bool ps = psum_go;
     ev.bytes = six ? lbytes : scan_bytes(P, C, B.need, masks, ps) + (ps ? psum_bytes(C, D, B.need) : 0.0);
     ev.pbytes = P.pat.rules.empty() ? 0.0 : (double)C.doc.size() * 4.0 + (double)C.n * (8.0 + 2.0 * (double)R);
@@ -1525,11 +1538,16 @@ kpe_status launch_lean_run(kpe_device* dev, const kpe_program* pp, std::vector<k
     }
     double bytes = 0;
     if (kpe_status st = lean6_launch(dev, P, PD, run.data() + i, cnt, masks, s, &bytes)) return st;
+    if (dev->timing) HIPCHK(hipEventRecord(ev.c, s));
+    bool retired = false;  // this launch's shards with retired rows: one pass each, behind the launch
+    for (size_t k = 0; k < cnt; ++k) {
+      retired = retired || !run[i + k]->retired.empty();
+      if (kpe_status st = retire_pass(run[i + k], (uint32_t)P.rules.size(), masks, s)) return st;
+    }
     i += cnt;
     if (dev->timing) {
-      HIPCHK(hipEventRecord(ev.c, s));
       HIPCHK(hipEventRecord(ev.d, s));
-      ev.bytes = bytes, ev.pbytes = 0, ev.kind = KPE_SCAN_BATCHED, ev.pre = ev.post = false;
+      ev.bytes = bytes, ev.pbytes = 0, ev.kind = KPE_SCAN_BATCHED, ev.pre = false, ev.post = retired;
       dev->pending.push_back(ev);
     }
   }
@@ -1766,6 +1784,7 @@ kpe_status kpe_corpus_upload(kpe_device* dev, kpe_corpus* cc) {
   HIPCHK(upload(D.pann_kv, C.pann_kv, s));
   HIPCHK(upload(D.c_sann, C.c_sann, s));
   HIPCHK(upload(D.limit_rows, C.limit_rows, s));
+  if (!cc->retired.empty()) HIPCHK(upload(D.retired, cc->retired, s));  // the set outlives an upload
   if (C.has_docs) {
     HIPCHK(upload(D.doc, C.doc, s));
     HIPCHK(upload(D.doc_off, C.doc_off, s));
@@ -1810,6 +1829,44 @@ kpe_status kpe_corpus_upload(kpe_device* dev, kpe_corpus* cc) {
             std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count());
   dev->up_alloc_s = dev->up_copy_s = 0;
   return KPE_OK;
+}
+
+kpe_status kpe_corpus_retire_rows(kpe_device* dev, kpe_corpus* c, const uint64_t* rows, uint64_t n) {
+  if (!c || (n && !rows)) return fail(KPE_E_INVALID, "null argument");
+  const uint64_t N = (uint64_t)c->c->n;
+  for (uint64_t i = 0; i < n; ++i)
+    if (rows[i] >= N) return fail(KPE_E_INVALID, "retired row past the corpus");
+  if (c->d && (!dev || dev->ordinal != c->d->ordinal))
+    return fail(KPE_E_STATE, "the corpus is uploaded: retire its rows on its own device");
+  if (!n) return KPE_OK;
+  std::vector<uint32_t> merged(c->retired);
+  for (uint64_t i = 0; i < n; ++i) merged.push_back((uint32_t)rows[i]);
+  std::sort(merged.begin(), merged.end());
+  merged.erase(std::unique(merged.begin(), merged.end()), merged.end());
+  if (merged.size() == c->retired.size()) return KPE_OK;  // nothing new
+  if (!c->d) {  // recorded here; the next upload sends it
+    c->retired.swap(merged);
+    return KPE_OK;
+  }
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  auto& D = *c->d;
+  // On the stream of the corpus's last evaluation: behind that evaluation's own pass over the
+  // list, and waited for, so ahead of the next evaluation whichever stream it takes. The buffer
+  // grows by doubling (freeing the old one waits for its readers).
+  hipStream_t s = D.bind.last ? D.bind.last : dev->stream;
+  if (D.retired.bytes < merged.size() * 4) HIPCHK(D.retired.ensure(std::max<size_t>(2 * merged.size(), 1024) * 4));
+  HIPCHK(hipMemcpyAsync(D.retired.p, merged.data(), merged.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+  c->retired.swap(merged);
+  return KPE_OK;
+}
+
+int64_t kpe_corpus_retired_rows(const kpe_corpus* c, uint64_t* rows, uint64_t cap) {
+  if (!c || (cap && !rows)) return -(int64_t)fail(KPE_E_INVALID, "null argument");
+  const uint64_t m = std::min<uint64_t>(c->retired.size(), cap);
+  for (uint64_t i = 0; i < m; ++i) rows[i] = c->retired[i];
+  return (int64_t)c->retired.size();
 }
 
 kpe_status kpe_evaluate_async(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c) {

@@ -2,6 +2,9 @@
 //  kpe_count_kernel      — per-rule status histogram (the CLI totals of
 //                          cmd/cli/kubectl-kyverno/processor/result.go:34-68); fetch time.
 //  kpe_fill_rows_kernel, kpe_apply_one_kernel — rows past an encoding limit, applyRules: One.
+//  kpe_retire_rows_kernel — retired rows (kpe_corpus_retire_rows): no response, last of all.
+//  kpe_delta_pairs_kernel, kpe_pair_rows_kernel, kpe_fp_pairs_kernel — a delta corpus's rows against
+//                          the kept rows of another corpus they replace (kpe_changed_pairs[_fp]).
 //  kpe_pack3_kernel      — the 3-bit verdict exchange.
 //  kpe_select_*_kernel, kpe_row_summary_kernel — sparse result fetch.
 //  kpe_ns_count*_kernel  — per-namespace rule counts.
@@ -104,6 +107,47 @@ extern "C" hipError_t kpe_launch_apply_one(uint8_t* verdicts, uint32_t* masks, i
   if (n <= 0 || nsegs == 0) return hipSuccess;
   hipLaunchKernelGGL(kpe_apply_one_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, verdicts, masks,
                      (uint32_t)n, R, reinterpret_cast<const uint2*>(segs), nsegs);
+  return hipGetLastError();
+}
+
+// Retired rows (kpe_corpus_retire_rows): every cell KPE_NA, every check mask word 0, after every
+// other kernel of the evaluation. A row is R contiguous bytes from byte row * R of a 4-byte aligned
+// matrix: the bytes before the first aligned word (head, at most 3), whole words, the bytes after
+// the last one (tail, at most 3). A row takes W = R / 4 + 2 work items (the head, R / 4 word slots,
+// the tail) and, with masks, R more (one per mask word); a thread takes one item at a time. A row
+// that ends before its first aligned word is all head.
+__global__ void __launch_bounds__(256) kpe_retire_rows_kernel(uint8_t* verdicts, uint32_t* masks, uint32_t R,
+                                                              const uint32_t* rows, uint32_t nrows) {
+  const uint32_t W = R / 4u + 2u, per = W + (masks ? R : 0u);
+  const uint64_t items = (uint64_t)nrows * per;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < items; i += (uint64_t)gridDim.x * 256u) {
+    const uint64_t k = i / per;
+    const uint32_t j = (uint32_t)(i - k * per);
+    const uint64_t b0 = (uint64_t)rows[k] * R, b1 = b0 + R;
+    if (j >= W) {
+      masks[b0 + (j - W)] = 0u;
+      continue;
+    }
+    const uint64_t up = (b0 + 3u) & ~(uint64_t)3u, dn = b1 & ~(uint64_t)3u;
+    const uint64_t a = up < b1 ? up : b1;  // end of the head
+    const uint64_t e = a > dn ? a : dn;    // end of the words
+    if (j == 0u) {
+      for (uint64_t b = b0; b < a; ++b) verdicts[b] = KPE_NA_;
+    } else if (j == W - 1u) {
+      for (uint64_t b = e; b < b1; ++b) verdicts[b] = KPE_NA_;
+    } else {
+      const uint64_t w = a + 4u * (uint64_t)(j - 1u);
+      if (w + 4u <= e) *reinterpret_cast<uint32_t*>(verdicts + w) = 0u;  // KPE_NA_ x 4; w is a multiple of 4 here
+    }
+  }
+}
+static_assert(KPE_NA_ == 0, "a retired row's words are zero");
+extern "C" hipError_t kpe_launch_retire_rows(uint8_t* verdicts, uint32_t* masks, uint32_t R, const uint32_t* rows,
+                                             uint32_t nrows, hipStream_t s) {
+  const uint64_t items = (uint64_t)nrows * (R / 4u + 2u + (masks ? R : 0u));
+  if (!nrows || !R) return hipSuccess;
+  const dim3 grid((unsigned)std::min<uint64_t>((items + 255u) / 256u, 1u << 16));
+  hipLaunchKernelGGL(kpe_retire_rows_kernel, grid, dim3(256), 0, s, verdicts, masks, R, rows, nrows);
   return hipGetLastError();
 }
 
@@ -585,6 +629,67 @@ extern "C" hipError_t kpe_launch_delta_transitions(const uint8_t* vnew, const ui
   return hipSuccess;
 }
 
+// Result deltas across corpora (kpe_changed_pairs): pair k = {new_row, old_row}, row new_row of the
+// new matrix against row old_row of another corpus's kept one, by the rules of the flag pass above.
+// A delta is small (thousands of pairs) and its rows are scattered: no staging of rows. The tables
+// are staged in LDS; a wave takes one pair at a time, lanes over the columns, and lane 0 writes the
+// pair's byte once. The changed pairs are the selection chain over those bytes, as for the rows.
+__global__ void __launch_bounds__(256) kpe_delta_pairs_kernel(const uint8_t* __restrict__ vnew,
+                                                              const uint8_t* __restrict__ vold,
+                                                              const uint64_t* __restrict__ pairs, uint64_t npairs,
+                                                              uint32_t Rn, uint32_t Ro, const uint32_t* __restrict__ tab,
+                                                              const uint8_t* __restrict__ unmapped,
+                                                              uint8_t* __restrict__ flags) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_delta[];
+  const uint32_t t = threadIdx.x, lane = t & 63u;
+  uint32_t* s_tab = reinterpret_cast<uint32_t*>(s_delta);
+  uint8_t* s_unm = s_delta + delta_up16(Rn * 4u);
+  for (uint32_t i = t; i < Rn; i += 256u) s_tab[i] = tab[i];
+  if (unmapped)
+    for (uint32_t i = t; i < Ro; i += 256u) s_unm[i] = unmapped[i];
+  __syncthreads();
+  const uint64_t nw = (uint64_t)gridDim.x * 4u;
+  for (uint64_t k = (uint64_t)blockIdx.x * 4u + (t >> 6); k < npairs; k += nw) {  // no barrier below
+    const uint8_t* nr = vnew + pairs[2u * k] * Rn;
+    const uint8_t* od = vold + pairs[2u * k + 1u] * Ro;
+    bool ch = false;
+    for (uint32_t r = lane; r < Rn; r += 64u) {
+      const uint32_t x = nr[r], e = s_tab[r], m = e & 0xFFFFu;
+      const uint32_t o = m != kDeltaNone ? (uint32_t)od[m] : 0u;
+      ch = ch || x != o || (x < 8u && ((e >> (16u + x)) & 1u));
+    }
+    if (unmapped)  // uniform: a response in a kept column no new column names
+      for (uint32_t o = lane; o < Ro; o += 64u) ch = ch || (s_unm[o] && od[o] != 0u);
+    const bool any = __ballot(ch) != 0ull;
+    if (lane == 0u) flags[k] = any ? 1u : 0u;
+  }
+}
+// out[i] = the new row of pair idx[i]: the row list kpe_gather_rows_kernel takes
+__global__ void __launch_bounds__(256) kpe_pair_rows_kernel(const uint64_t* __restrict__ pairs,
+                                                            const uint64_t* __restrict__ idx, uint64_t m,
+                                                            uint64_t* __restrict__ out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < m; i += (uint64_t)gridDim.x * 256u)
+    out[i] = pairs[2u * idx[i]];
+}
+extern "C" hipError_t kpe_launch_delta_pairs(const uint8_t* vnew, const uint8_t* vold, const uint64_t* pairs,
+                                             uint64_t npairs, uint32_t Rn, uint32_t Ro, const uint32_t* tab,
+                                             const uint8_t* unmapped, uint8_t* flags, hipStream_t s) {
+  if (!npairs) return hipSuccess;
+  if (Rn > kDeltaMaxRules || Ro > kDeltaMaxRules) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)std::min<uint64_t>((npairs + 3u) / 4u, kDeltaGrid));
+  const size_t dyn = (size_t)delta_up16(Rn * 4u) + delta_up16(Ro) + 16u;
+  hipLaunchKernelGGL(kpe_delta_pairs_kernel, grid, dim3(256), dyn, s, vnew, vold, pairs, npairs, Rn, Ro, tab, unmapped,
+                     flags);
+  return hipGetLastError();
+}
+extern "C" hipError_t kpe_launch_pair_rows(const uint64_t* pairs, const uint64_t* idx, uint64_t m, uint64_t* out,
+                                           hipStream_t s) {
+  if (!m) return hipSuccess;
+  const dim3 grid((unsigned)std::min<uint64_t>((m + 255u) / 256u, 1u << 16));
+  hipLaunchKernelGGL(kpe_pair_rows_kernel, grid, dim3(256), 0, s, pairs, idx, m, out);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // Row fingerprints (kpe_fetch_row_fingerprints, kpe_fingerprints_keep, kpe_changed_rows_fp): 8 bytes
 // per row, the shape of kpe_row_summary_kernel (fp.inl, shared with scripts/fp_check.cpp). The
@@ -675,6 +780,61 @@ extern "C" hipError_t kpe_launch_fp_gather(const uint64_t* fp, const uint64_t* r
   if (!m) return hipSuccess;
   const dim3 grid((unsigned)std::min<uint64_t>((m + 255u) / 256u, 1u << 16));
   hipLaunchKernelGGL(kpe_fp_gather_kernel, grid, dim3(256), 0, s, fp, rows, m, out);
+  return hipGetLastError();
+}
+
+// The fingerprint form of kpe_delta_pairs_kernel (kpe_changed_pairs_fp): pair k = {new_row,
+// old_row}; fp_out[k] = the fingerprint of row new_row (fp.inl's cell hash, summed over the row by
+// the wave: lanes over the columns, then a butterfly of 64-bit adds), flags[k] = it differs from
+// kept[old_row]. lds != 0: both salt tables staged in dynamic LDS (R <= kFpLdsRules).
+template <bool MASKS>
+__global__ void __launch_bounds__(256) kpe_fp_pairs_kernel(const uint8_t* __restrict__ v, const uint32_t* __restrict__ masks,
+                                                           uint32_t R, const uint64_t* __restrict__ pairs, uint64_t npairs,
+                                                           const uint64_t* __restrict__ tbl_g, uint32_t lds,
+                                                           uint32_t msg_codes, const uint64_t* __restrict__ kept,
+                                                           uint64_t* __restrict__ fp_out, uint8_t* __restrict__ flags) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_fp_dyn[];
+  const uint32_t t = threadIdx.x, lane = t & 63u;
+  const uint64_t* tbl = tbl_g;
+  if (lds) {  // uniform
+    uint64_t* l = reinterpret_cast<uint64_t*>(s_fp_dyn);
+    for (uint32_t i = t; i < 2u * R; i += 256u) l[i] = tbl_g[i];
+    tbl = l;
+  }
+  __syncthreads();
+  const uint64_t nw = (uint64_t)gridDim.x * 4u;
+  for (uint64_t k = (uint64_t)blockIdx.x * 4u + (t >> 6); k < npairs; k += nw) {  // no barrier below
+    const uint64_t c0 = pairs[2u * k] * R;
+    uint64_t acc = 0;
+    for (uint32_t col = lane; col < R; col += 64u) {
+      const uint32_t x = v[c0 + col];
+      if (x == 0u) continue;
+      uint32_t m = 0;
+      if (MASKS && x == 2u) m = masks[c0 + col];
+      acc += fp_cell(x, m, tbl, col, R, msg_codes);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += (uint64_t)__shfl_xor((unsigned long long)acc, off, 64);
+    if (lane == 0u) {
+      fp_out[k] = acc;
+      flags[k] = acc != kept[pairs[2u * k + 1u]] ? 1u : 0u;
+    }
+  }
+}
+extern "C" hipError_t kpe_launch_fp_pairs(const uint8_t* v, const uint32_t* masks, uint32_t R, const uint64_t* pairs,
+                                          uint64_t npairs, const uint64_t* tbl, uint32_t msg_codes, const uint64_t* kept,
+                                          uint64_t* fp_out, uint8_t* flags, hipStream_t s) {
+  if (!npairs) return hipSuccess;
+  if (R > kFpMaxRules) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)std::min<uint64_t>((npairs + 3u) / 4u, kFpGrid));
+  const uint32_t lds = R && R <= kFpLdsRules ? 1u : 0u;
+  const size_t dyn = lds ? (size_t)R * 16u : 0u;
+  if (masks)
+    hipLaunchKernelGGL(kpe_fp_pairs_kernel<true>, grid, dim3(256), dyn, s, v, masks, R, pairs, npairs, tbl, lds, msg_codes,
+                       kept, fp_out, flags);
+  else
+    hipLaunchKernelGGL(kpe_fp_pairs_kernel<false>, grid, dim3(256), dyn, s, v, masks, R, pairs, npairs, tbl, lds, msg_codes,
+                       kept, fp_out, flags);
   return hipGetLastError();
 }
 

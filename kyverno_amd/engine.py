@@ -564,6 +564,89 @@ class Engine:
         k = min(total, n)
         return rows[:k], (vr[:k] if with_verdicts else np.zeros((0, R), dtype=np.uint8)), fps[:k], total
 
+    # ---- resource churn on a resident corpus (retired rows, delta corpora compared by pair) ----
+    def retire_rows(self, corpus: Corpus, rows):
+        """Retire rows of corpus (kpe_corpus_retire_rows): from the next evaluation on they give no
+        response to any consumer. The set only grows and survives a re-upload; a corpus that is
+        not uploaded records it on the host."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        check(load().kpe_corpus_retire_rows(self.device.h if corpus.device is not None else None, corpus.h,
+                                            r.ctypes.data if r.size else None, r.size))
+
+    def retired_rows(self, corpus: Corpus) -> np.ndarray:
+        """The retired rows of corpus, ascending and unique (kpe_corpus_retired_rows): uint64."""
+        L = load()
+        n = int(L.kpe_corpus_retired_rows(corpus.h, None, 0))
+        out = np.zeros(max(n, 0), dtype=np.uint64)
+        if n > 0:
+            L.kpe_corpus_retired_rows(corpus.h, out.ctypes.data, n)
+        return out
+
+    @staticmethod
+    def _pairs(pairs):
+        p = np.ascontiguousarray(pairs, dtype=np.uint64).reshape(-1, 2)
+        return p, (p if p.size else np.zeros((1, 2), dtype=np.uint64))
+
+    def changed_pairs(self, ps: PolicySet, new: Corpus, old: Corpus, pairs, column_map=None, always=0,
+                      cap: Optional[int] = None, with_verdicts=True):
+        """For pairs (k, 2) of (row of new, row of old): the pairs whose row of the last evaluation
+        of ps on `new` differs from the paired row of `old`'s kept result, by the rules of
+        changed_rows (kpe_changed_pairs): (pair indices uint64 ascending, their new verdict rows
+        (m, R) uint8, total). column_map, always, cap as in changed_rows."""
+        L = load()
+        R = ps.num_rules
+        p, pbuf = self._pairs(pairs)
+        mbuf = self._delta_map(ps, column_map)
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(always, dtype=np.uint8), (R,)) if np.ndim(always) == 0
+                                 else np.asarray(always, dtype=np.uint8))
+        if a.shape != (R,):
+            raise ValueError("always: one mask, or one per rule")
+        abuf = a if R else np.zeros(1, dtype=np.uint8)
+
+        def call(idx, vr, n):
+            t = L.kpe_changed_pairs(self.device.h, ps.h, new.h, old.h, pbuf.ctypes.data, len(p),
+                                    None if mbuf is None else mbuf.ctypes.data, abuf.ctypes.data,
+                                    idx.ctypes.data if n else None,
+                                    vr.ctypes.data if (vr is not None and n and R) else None, n)
+            if t < 0:
+                check(-t)
+            return int(t)
+
+        n = call(None, None, 0) if cap is None else min(int(cap), len(p))
+        idx = np.zeros(n, dtype=np.uint64)
+        vr = np.zeros((n, R), dtype=np.uint8) if with_verdicts else None
+        total = call(idx, vr, n) if (n or cap is not None) else 0
+        k = min(total, n)
+        return idx[:k], (vr[:k] if with_verdicts else np.zeros((0, R), dtype=np.uint8)), total
+
+    def changed_pairs_fp(self, ps: PolicySet, new: Corpus, old: Corpus, pairs, salts=None, msg_salts=None,
+                         msg_codes=None, masks=False, cap: Optional[int] = None, with_verdicts=True):
+        """The fingerprint form (kpe_changed_pairs_fp): the pairs whose new row's fingerprint differs
+        from `old`'s kept fingerprint of the paired row: (pair indices, their new verdict rows, their
+        new fingerprints, total). Arguments as changed_rows_fp."""
+        L = load()
+        R = ps.num_rules
+        p, pbuf = self._pairs(pairs)
+        s, ms, mc = _fp_salts(R, salts, msg_salts, msg_codes)
+        fl = FP_MASKS if masks else 0
+
+        def call(idx, vr, fps, n):
+            t = L.kpe_changed_pairs_fp(self.device.h, ps.h, new.h, old.h, pbuf.ctypes.data, len(p), _ptr(s), _ptr(ms),
+                                       mc, fl, idx.ctypes.data if n else None,
+                                       vr.ctypes.data if (vr is not None and n and R) else None,
+                                       fps.ctypes.data if n else None, n)
+            if t < 0:
+                check(-t)
+            return int(t)
+
+        n = call(None, None, None, 0) if cap is None else min(int(cap), len(p))
+        idx = np.zeros(n, dtype=np.uint64)
+        fps = np.zeros(n, dtype=np.uint64)
+        vr = np.zeros((n, R), dtype=np.uint8) if with_verdicts else None
+        total = call(idx, vr, fps, n) if (n or cap is not None) else 0
+        k = min(total, n)
+        return idx[:k], (vr[:k] if with_verdicts else np.zeros((0, R), dtype=np.uint8)), fps[:k], total
+
     def pattern_traces(self, ps: PolicySet, corpus: Corpus, cells) -> np.ndarray:
         """Failing-path records of pattern cells (kpe_pattern_traces) after an evaluation of ps on
         corpus: cells = flat indices row * R + column; returns (len(cells), KPE_TRACE_ROOTS,

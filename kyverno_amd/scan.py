@@ -71,6 +71,146 @@ def _key(row: bytes, i: int):
     return (d.get("apiVersion"), d.get("kind"), meta.get("namespace"), meta.get("name"))
 
 
+class RowMap:
+    """Bookkeeping of a resident corpus under resource churn; no device, no library.
+
+    Resources live in segments (corpora): segment 0 is the corpus the scanner was built over, every
+    `update` that flattens something appends one. A resource has a logical row for life: the
+    initial rows are 0..n-1, new resources are appended, a deleted resource's index is never
+    reused. A replaced or deleted resource's physical row is retired in its segment. The map
+    holds logical row -> (segment, row), its inverse per segment, key -> logical row and the
+    resource hash per logical row.
+
+    Compaction (one segment again, live rows in logical order) is due past `max_segments`
+    segments or once more than `max_retired` of the physical rows are retired."""
+
+    def __init__(self, keys, hashes, max_segments=16, max_retired=0.25):
+        keys, hashes = list(keys), list(hashes)
+        if len(keys) != len(hashes):
+            raise ValueError("one hash per key")
+        self.max_segments, self.max_retired = int(max_segments), float(max_retired)
+        self.loc = [(0, i) for i in range(len(keys))]  # logical row -> (segment, row), None: deleted
+        self.back = [list(range(len(keys)))]  # per segment: row -> logical row, -1: retired
+        self.hashes = hashes  # per logical row (None: deleted)
+        self.keys = keys
+        self.index = {k: i for i, k in enumerate(keys)}  # a key that occurs twice names its last row
+        self.retired = 0
+
+    @property
+    def n_logical(self):
+        return len(self.loc)
+
+    @property
+    def n_physical(self):
+        return sum(len(b) for b in self.back)
+
+    @property
+    def n_live(self):
+        return self.n_physical - self.retired
+
+    @property
+    def segments(self):
+        return len(self.back)
+
+    def live(self):
+        """The live logical rows, ascending."""
+        return [i for i, p in enumerate(self.loc) if p is not None]
+
+    def row_of(self, key_or_row):
+        """The live logical row a key or a logical row names, or None."""
+        if isinstance(key_or_row, (int, np.integer)) and not isinstance(key_or_row, bool):
+            i = int(key_or_row)
+            return i if 0 <= i < len(self.loc) and self.loc[i] is not None else None
+        return self.index.get(key_or_row)
+
+    def plan(self, upserts, deletes=()):
+        """What an update does, without doing it. upserts: (key, hash) per offered resource;
+        deletes: keys or logical rows. Returns a dict: `items`, a list of (offered index, logical
+        row or None for a new resource) to flatten, in offered order; `skipped`, the offered
+        resources whose hash equals the stored one; `deletes`, the logical rows to delete,
+        ascending. A key offered twice counts once, by its last occurrence; a resource both
+        offered and deleted is deleted. NO_HASH never equals a stored hash."""
+        dele = sorted({r for r in (self.row_of(d) for d in deletes) if r is not None})
+        dead = set(dele)
+        last = {}
+        for i, (k, _) in enumerate(upserts):
+            last[k] = i
+        items, skipped = [], 0
+        for i, (k, h) in enumerate(upserts):
+            if last[k] != i:
+                continue
+            l = self.index.get(k)
+            if l is not None and l in dead:
+                continue
+            if l is not None and h != NO_HASH and self.hashes[l] == h:
+                skipped += 1
+                continue
+            items.append((i, l))
+        return {"items": items, "skipped": skipped, "deletes": dele, "upserts": list(upserts)}
+
+    def _retire(self, l, out):
+        s, r = self.loc[l]
+        self.back[s][r] = -1
+        self.retired += 1
+        out.setdefault(s, []).append(r)
+
+    def commit(self, plan):
+        """Apply a plan: its items become the rows of a new segment, in order. Returns (the new
+        segment or None when nothing was flattened, the logical row of each item, {segment:
+        rows to retire there})."""
+        retire, rows = {}, []
+        seg = len(self.back) if plan["items"] else None
+        if seg is not None:
+            self.back.append([])
+        for j, (i, l) in enumerate(plan["items"]):
+            k, h = plan["upserts"][i]
+            if l is None:
+                l = len(self.loc)
+                self.loc.append(None)
+                self.hashes.append(None)
+                self.keys.append(k)
+                self.index[k] = l
+            else:
+                self._retire(l, retire)
+            self.loc[l], self.hashes[l] = (seg, j), h
+            self.back[seg].append(l)
+            rows.append(l)
+        for l in plan["deletes"]:
+            self._retire(l, retire)
+            self.loc[l], self.hashes[l] = None, None
+            if self.index.get(self.keys[l]) == l:
+                del self.index[self.keys[l]]
+        return seg, rows, retire
+
+    def translate(self, seg, rows):
+        """(position in rows, logical row) of the rows of a segment's row list that are live; rows
+        of retired physical rows are dropped: their resource lives elsewhere, or nowhere."""
+        b = self.back[seg]
+        return [(k, b[int(r)]) for k, r in enumerate(rows) if b[int(r)] >= 0]
+
+    def group(self, rows):
+        """{segment: [(logical row, row)]} of live logical rows, in the order given."""
+        out = {}
+        for l in rows:
+            p = self.loc[int(l)]
+            if p is not None:
+                out.setdefault(p[0], []).append((int(l), p[1]))
+        return out
+
+    def needs_compaction(self):
+        return self.segments > self.max_segments or self.retired > self.max_retired * self.n_physical
+
+    def compact(self):
+        """One segment again: the live logical rows, ascending, become its rows 0..m-1. Logical
+        indices do not move. Returns the live rows."""
+        live = self.live()
+        for j, l in enumerate(live):
+            self.loc[l] = (0, j)
+        self.back = [list(live)]
+        self.retired = 0
+        return live
+
+
 class BackgroundScanner:
     """Verdict rows of the last scan per resource; `scan` evaluates what changed."""
 
@@ -126,13 +266,25 @@ class ResidentScanner:
     background/controller.go:379-419,463; ReportsAreIdentical, pkg/controllers/report/utils/
     utils.go:66-88). Here the last result stays on the device (Engine.keep_results, or with
     keep="fingerprints" Engine.keep_fingerprints) and the comparison runs there (Engine.changed_rows,
-    Engine.changed_rows_fp): the unchanged rows never cross to the host."""
+    Engine.changed_rows_fp): the unchanged rows never cross to the host.
+
+    With keyed=True the corpus also follows resource events (controller.go:247-297): `update`
+    flattens only the resources whose hash changed into a delta segment, compares them on the device
+    with the kept rows they replace and retires those rows where they were; the corpus, its upload
+    and its kept results stay. Rows are then logical rows (RowMap)."""
 
     MESSAGE_CODES = SEL(2) | SEL(4) | SEL(5)  # FAIL, ERROR, SKIP: results whose message the policy text decides
 
     def __init__(self, engine, ndjson: bytes, ns_labels=None, keep="matrix", fingerprints=None, edits=None,
-                 reports=False):
-        """reports=True: the scanner keeps the NDJSON lines and evaluates with check masks, so that
+                 reports=False, keyed=False, max_segments=16, max_retired=0.25):
+        """keyed=True: the scanner also follows resource churn (`update`, `compact`, `matrix`). It
+        then keeps the NDJSON lines, the resource-key index and the per-row resource hash
+        (`resource_hashes`), and holds the corpus as segments (RowMap). `update` compacts past
+        max_segments segments or once more than max_retired of the physical rows are retired; both
+        defaults are unmeasured guesses (every segment adds launches to an `apply`, every retired
+        row is scanned for nothing), not tuned values. Without keyed the class is what it was.
+
+        reports=True: the scanner keeps the NDJSON lines and evaluates with check masks, so that
         `reports(rows)` can render the PolicyReport results of rows of the last applied PolicySet.
 
         keep="matrix" (the default): the last verdict matrix stays on the device (N x R bytes) and
@@ -148,20 +300,55 @@ class ResidentScanner:
         self.engine = engine
         self.keep = keep
         nsl = json.dumps(ns_labels).encode() if isinstance(ns_labels, dict) else ns_labels
+        self._nsl = nsl
         self.corpus = Corpus(ndjson, nsl).upload(engine.device)
         self._policies = None  # the PolicySet of the kept result (held while its matrix is kept)
         self._with_reports = bool(reports)
-        self._lines = ndjson_rows(ndjson) if reports else None  # row i of the corpus is line i
+        self._keyed = bool(keyed)
+        self._lines = ndjson_rows(ndjson) if (reports or keyed) else None  # logical row i is line i
+        self._segs = [self.corpus]  # keyed: the segments (RowMap); segment 0 is self.corpus
+        self._map = None
+        self._updated = False
+        self._msg = None  # keep="fingerprints": the msg_salts of the last apply
+        if keyed:
+            if len(self._lines) != self.corpus.n:
+                raise KpeError(2, "keyed: one NDJSON line per corpus row")  # KPE_E_INVALID
+            self._map = RowMap([_key(r, i) for i, r in enumerate(self._lines)],
+                               resource_hashes(b"\n".join(self._lines)), max_segments, max_retired)
         self._applied = None  # the PolicySet of the last apply (what `reports` renders)
         self.edits = dict(edits or {})  # policy name -> edits seen (keep="fingerprints": folded into msg_salts)
         if fingerprints is not None:
             engine.load_fingerprints(self.corpus, fingerprints)
         self.last_stats = {}
 
+    @property
+    def resource_hashes(self):
+        """keyed: CalculateResourceHash per logical row (None for a deleted resource)."""
+        return None if self._map is None else list(self._map.hashes)
+
     def fingerprints(self):
         """keep="fingerprints": the kept fingerprints, one uint64 per row (None before the first
-        apply): what a caller stores with the reports, together with `edits`."""
-        return self.engine.kept_fingerprints(self.corpus) if self.keep == "fingerprints" else None
+        apply): what a caller stores with the reports, together with `edits`. Once an `update` has
+        happened: (rows, fps), the live logical rows and one value for each."""
+        if self.keep != "fingerprints":
+            return None
+        if not self._updated:
+            return self.engine.kept_fingerprints(self.corpus)
+        if self.engine.kept_fingerprints(self._segs[0], 0, 0) is None:
+            return None
+        live = np.array(self._map.live(), dtype=np.uint64)
+        return live, self._fps_by_row()[live.astype(np.int64)]
+
+    def _fps_by_row(self):
+        """The kept fingerprints by logical row (0 where nothing is kept, or nothing lives)."""
+        out = np.zeros(self._map.n_logical, dtype=np.uint64)
+        for s, seg in enumerate(self._segs):
+            fp = self.engine.kept_fingerprints(seg)
+            if fp is None:
+                continue
+            back = np.array(self._map.back[s], dtype=np.int64)
+            out[back[back >= 0]] = fp[back >= 0]
+        return out
 
     def _apply_fp(self, policies, edited):
         eng, corpus = self.engine, self.corpus
@@ -170,6 +357,9 @@ class ResidentScanner:
         msg = rule_salts(policies)
         for r, n in enumerate(policies.rule_names):
             msg[r] ^= np.uint64(self.edits.get(n.split("/", 1)[0], 0))
+        self._msg = msg
+        if self._keyed:
+            return self._apply_segments(policies, None, msg)
         eng.evaluate_async(policies, corpus, masks=self._with_reports)
         self._applied = policies
         if eng.kept_fingerprints(corpus, 0, 0) is None:
@@ -189,6 +379,10 @@ class ResidentScanner:
         if self.keep == "fingerprints":
             return self._apply_fp(policies, edited)
         eng, corpus = self.engine, self.corpus
+        if self._keyed:
+            names = set(edited)
+            return self._apply_segments(policies, np.array(
+                [self.MESSAGE_CODES if n.split("/", 1)[0] in names else 0 for n in policies.rule_names], dtype=np.uint8), None)
         eng.evaluate_async(policies, corpus, masks=self._with_reports)
         self._applied = policies
         if self._policies is None:
@@ -215,5 +409,163 @@ class ResidentScanner:
         if self._applied is None:
             raise KpeError(5, "no apply yet")
         rows = [int(i) for i in rows]
-        res = self.engine.report_rows(self._applied, self.corpus, rows, resources=[self._lines[i] for i in rows])
-        return dict(zip(rows, res))
+        if not self._keyed:
+            res = self.engine.report_rows(self._applied, self.corpus, rows, resources=[self._lines[i] for i in rows])
+            return dict(zip(rows, res))
+        out = {i: [] for i in rows}  # a deleted resource has no report
+        for s, pr in self._map.group(rows).items():
+            res = self.engine.report_rows(self._applied, self._segs[s], [r for _, r in pr],
+                                          resources=[self._lines[l] for l, _ in pr])
+            out.update(zip((l for l, _ in pr), res))
+        return out
+
+    # ---- resource churn (keyed=True) ----
+    def _need_keyed(self):
+        if not self._keyed:
+            raise KpeError(5, "ResidentScanner(keyed=True) follows resource churn")  # KPE_E_STATE
+
+    def _apply_segments(self, policies, always, msg):
+        """`apply` over the segments: one batch evaluation, the per-segment changed rows translated
+        to logical rows (rows of retired physical rows dropped). always: keep="matrix"; msg: the
+        msg_salts of keep="fingerprints"."""
+        eng, m = self.engine, self._map
+        eng.evaluate_batch_async(policies, self._segs, masks=self._with_reports)
+        self._applied = policies
+        out = {}
+        for s, seg in enumerate(self._segs):
+            if msg is not None:
+                if eng.kept_fingerprints(seg, 0, 0) is None:  # against "no report": every row with a response
+                    eng.load_fingerprints(seg, np.zeros(seg.n, dtype=np.uint64))
+                rows, vr, _, _ = eng.changed_rows_fp(policies, seg, msg_salts=msg, msg_codes=self.MESSAGE_CODES)
+                eng.keep_fingerprints(policies, seg, msg_salts=msg, msg_codes=self.MESSAGE_CODES)
+            elif self._policies is None:  # nothing to compare with: the whole matrix, once
+                v, _, _ = eng.fetch(policies, seg)
+                rows = np.flatnonzero((v != 0).any(axis=1))
+                vr = v[rows]
+            else:
+                rows, vr, _ = eng.changed_rows(policies, seg, always=always)
+            for k, l in m.translate(s, rows):
+                out[l] = vr[k].copy()
+            if msg is None:
+                eng.keep_results(policies, seg)
+        if msg is None:
+            self._policies = policies
+        self.last_stats = {"rows": m.n_live, "changed": len(out), "segments": len(self._segs)}
+        return out
+
+    def _keep(self, seg):
+        """Keep the last evaluation of the applied PolicySet on seg, as `apply` does."""
+        if self.keep == "fingerprints":
+            self.engine.keep_fingerprints(self._applied, seg, msg_salts=self._msg, msg_codes=self.MESSAGE_CODES)
+        else:
+            self.engine.keep_results(self._applied, seg)
+
+    def update(self, upserts: bytes = b"", deletes=()):
+        """Resource events between two policy changes (background/controller.go:247-297,
+        needsReconcile): `upserts` is NDJSON of created or changed resources, `deletes` keys (as
+        `_key` makes them) or logical rows. Returns {logical row: verdict row, or None for a deleted
+        resource} of exactly the rows whose report changes under the last applied PolicySet.
+
+        An offered resource whose hash equals the stored one is dropped before flattening
+        (last_stats["skipped"]). The others are flattened into a delta segment, a corpus of its
+        own, evaluated with the last applied PolicySet; a replaced resource is compared on the
+        device with the kept result of the segment that held it (Engine.changed_pairs, or
+        changed_pairs_fp with keep="fingerprints"), a new one is reported when it has any response.
+        Then the delta segment's result is kept and the replaced and deleted rows are retired in
+        their old segments. Logical rows are stable: a resource keeps its index for life, new ones
+        are appended, a deleted one's is never reused. Before the first `apply` there is nothing
+        to compare: the corpus is restructured and {} returned."""
+        self._need_keyed()
+        eng, m = self.engine, self._map
+        lines = ndjson_rows(upserts)
+        offered = list(zip((_key(r, i) for i, r in enumerate(lines)), resource_hashes(b"\n".join(lines)))) if lines else []
+        plan = m.plan(offered, deletes)
+        items = plan["items"]
+        out = {}
+        fresh = {}  # row of the delta segment -> verdict row, of the new resources that have a response
+        seg = None
+        if items:
+            seg = Corpus(b"\n".join(lines[i] for i, _ in items), self._nsl).upload(eng.device)
+            if seg.n != len(items):
+                raise KpeError(2, "update: one corpus row per offered resource")  # KPE_E_INVALID
+        if self._applied is not None:
+            if seg is not None:
+                eng.evaluate_async(self._applied, seg, masks=self._with_reports)
+                by_old = {}  # old segment -> [(row of seg, logical row, old row)]
+                for j, (_, l) in enumerate(items):
+                    if l is not None:
+                        by_old.setdefault(m.loc[l][0], []).append((j, l, m.loc[l][1]))
+                for s, trip in by_old.items():
+                    pairs = np.array([(j, r) for j, _, r in trip], dtype=np.uint64)
+                    if self.keep == "fingerprints":
+                        idx, vr, _, _ = eng.changed_pairs_fp(self._applied, seg, self._segs[s], pairs, msg_salts=self._msg,
+                                                             msg_codes=self.MESSAGE_CODES)
+                    else:
+                        idx, vr, _ = eng.changed_pairs(self._applied, seg, self._segs[s], pairs)
+                    for k, i in enumerate(idx):
+                        out[trip[int(i)][1]] = vr[k].copy()
+                if any(l is None for _, l in items):  # the delta is small: its matrix, for the new resources
+                    v, _, _ = eng.fetch(self._applied, seg)
+                    fresh = {j: v[j].copy() for j, (_, l) in enumerate(items) if l is None and v[j].any()}
+                self._keep(seg)
+            for l in plan["deletes"]:
+                out[l] = None
+        new_seg, rows, retire = m.commit(plan)
+        if seg is not None:
+            self._segs.append(seg)
+            assert new_seg == len(self._segs) - 1
+            for j, l in enumerate(rows):
+                if l == len(self._lines):
+                    self._lines.append(None)
+                self._lines[l] = lines[items[j][0]]
+            for j, row in fresh.items():
+                out[rows[j]] = row
+        for l in plan["deletes"]:
+            self._lines[l] = None
+        for s, rr in retire.items():
+            eng.retire_rows(self._segs[s], rr)
+        self._updated = True
+        self.last_stats = {"rows": m.n_live, "offered": len(lines), "skipped": plan["skipped"], "rescanned": len(items),
+                           "deleted": len(plan["deletes"]), "changed": len(out), "segments": len(self._segs)}
+        if m.needs_compaction():
+            self.compact()
+            self.last_stats["segments"] = len(self._segs)
+            self.last_stats["compacted"] = True
+        return out
+
+    def compact(self):
+        """Re-flatten the live rows into one segment in logical order, evaluate the last applied
+        PolicySet on it and keep that result; with keep="fingerprints" the kept fingerprints are
+        carried over (Engine.load_fingerprints). The recompute reports nothing as changed: it is
+        the state the segments already held."""
+        self._need_keyed()
+        eng, m = self.engine, self._map
+        fps = self._fps_by_row() if self.keep == "fingerprints" else None
+        had_fps = fps is not None and eng.kept_fingerprints(self._segs[0], 0, 0) is not None
+        live = m.compact()
+        seg = Corpus(b"\n".join(self._lines[l] for l in live), self._nsl).upload(eng.device)
+        if seg.n != len(live):
+            raise KpeError(2, "compact: one corpus row per live resource")  # KPE_E_INVALID
+        self._segs = [seg]
+        self.corpus = seg
+        if self._applied is not None:
+            eng.evaluate_async(self._applied, seg, masks=self._with_reports)
+            if self.keep != "fingerprints":
+                eng.keep_results(self._applied, seg)
+        if had_fps:
+            eng.load_fingerprints(seg, fps[np.array(live, dtype=np.int64)])
+        self._updated = True
+
+    def matrix(self):
+        """The current verdict matrix by logical row under the last applied PolicySet (a deleted
+        resource's row is all NA): (logical rows, R) uint8. Diagnostics and tests: it fetches every
+        segment's matrix."""
+        self._need_keyed()
+        if self._applied is None:
+            raise KpeError(5, "no apply yet")
+        out = np.zeros((self._map.n_logical, self._applied.num_rules), dtype=np.uint8)
+        for s, seg in enumerate(self._segs):
+            v, _, _ = self.engine.fetch(self._applied, seg)
+            back = np.array(self._map.back[s], dtype=np.int64)
+            out[back[back >= 0]] = v[back >= 0]
+        return out
