@@ -201,6 +201,41 @@ kpe_status kpe_corpus_retire_rows(kpe_device* dev, kpe_corpus* c, const uint64_t
 /* The retired rows, ascending and unique: the first min(total, cap) into rows[]; returns the total
  * (rows == NULL with cap == 0 counts only), or -kpe_status. Host only. */
 int64_t kpe_corpus_retired_rows(const kpe_corpus* c, uint64_t* rows, uint64_t cap);
+/* Change the namespace label table of a flattened corpus in place (the labels of a Namespace
+ * changed; the reference reads them fresh at every rescan, background/controller.go:310-318).
+ * flags == 0 is a patch: every member "<namespace>": {...} of the JSON object sets that
+ * namespace's entry, its value read as kpe_corpus_flatten reads ns_labels_json (string-valued
+ * members are the labels, other members are skipped, a value that is no object gives an entry
+ * without labels); "<namespace>": null removes the entry; namespaces not named keep theirs; a key
+ * that occurs twice counts by its last occurrence; a null or empty argument changes nothing.
+ * KPE_NSL_REPLACE: the table becomes what kpe_corpus_flatten builds from this JSON (null, empty or
+ * {}: no table).
+ * After the call every consumer behaves as on a corpus flattened from the same NDJSON with the
+ * resulting table: verdicts, check masks, counts, namespace counts, kpe_cli_summary_ns, row
+ * summaries, fingerprints, report rows and traces. kpe_corpus_digest is not part of that: new label
+ * strings are appended to the label dictionaries, where a fresh flatten interns the table first, so
+ * the ids, and with them the digest, differ from a fresh corpus's. A namespace without an entry and
+ * one whose entry has no labels are the same to every consumer, before and after.
+ * *changed (may be NULL) receives the number of namespaces whose entry changed, labels compared as
+ * sets of (key, value) pairs. When it is 0 nothing is touched or invalidated.
+ * Otherwise the call waits for the corpus's last evaluation and leaves the corpus without one:
+ * the fetch, select and trace calls answer KPE_E_STATE until the next evaluation, which binds the
+ * program again in full. Kept results, kept fingerprints, the retired rows and the namespace groups
+ * (kpe_corpus_num_namespaces, kpe_corpus_row_namespaces: a namespace that only the table names is
+ * no group) stay. dev may be NULL for a corpus that is not uploaded: the table changes on the host
+ * and travels with the next upload. On an uploaded corpus the table (and the label dictionaries
+ * when they grew) are sent again on the corpus's stream and every row's table row is recomputed on
+ * the device from its namespace id; nothing proportional to the rows crosses the bus.
+ * KPE_E_INVALID for malformed JSON or a top level that is no object; KPE_E_STATE for an uploaded
+ * corpus with a null device or a device other than its own; both before anything changes. The call
+ * needs exclusive use of the corpus, as kpe_corpus_upload and kpe_corpus_retire_rows do. */
+#define KPE_NSL_REPLACE 1u
+kpe_status kpe_corpus_set_namespace_labels(kpe_device* dev, kpe_corpus* c, const char* ns_labels_json, size_t len,
+                                           uint32_t flags, uint64_t* changed /* may be NULL */);
+/* The current table as JSON, {"<namespace>": {"<key>": "<value>", ...}, ...} in table order (given
+ * back with KPE_NSL_REPLACE it rebuilds the same table): writes at most cap bytes into out (no
+ * terminator) and returns the length needed, or -kpe_status. Host only. */
+int64_t kpe_corpus_namespace_labels(const kpe_corpus* c, char* out, size_t cap);
 /* The corpus's per-pod PSA summary, built on dev (waits for it; builds it first when no LEAN
  * evaluation has yet): 2 words per row (include-free layout of kyverno_amd/csrc/schema.h PS_*:
  * x = OR of the pod's container state bitmaps, y = the list codes under the PSA library's fixed

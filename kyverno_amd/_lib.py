@@ -131,6 +131,10 @@ def load():
     L.kpe_corpus_retire_rows.restype = ctypes.c_int
     L.kpe_corpus_retired_rows.argtypes = [vp, vp, u64]
     L.kpe_corpus_retired_rows.restype = i64
+    L.kpe_corpus_set_namespace_labels.argtypes = [vp, vp, ctypes.c_char_p, ctypes.c_size_t, u32, vp]
+    L.kpe_corpus_set_namespace_labels.restype = ctypes.c_int
+    L.kpe_corpus_namespace_labels.argtypes = [vp, vp, ctypes.c_size_t]
+    L.kpe_corpus_namespace_labels.restype = i64
     L.kpe_changed_pairs.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64]
     L.kpe_changed_pairs.restype = i64
     L.kpe_changed_pairs_fp.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, u8, u32, vp, vp, vp, u64]

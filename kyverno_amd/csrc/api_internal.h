@@ -287,6 +287,7 @@ struct DeviceCorpus {
   DevBuf doc_perm;  // rows by descending tape size: the pattern / condition kernels' lane -> row map
   DevBuf limit_rows;                     // rows past a per-resource limit
   DevBuf retired;                        // kpe_corpus::retired (kpe_retire_rows_kernel reads it last)
+  DevBuf nsl_map;  // kpe_corpus_set_namespace_labels: namespace id -> table row (kpe_nsl_remap_kernel's input)
   // cold pod columns, uploaded on the first binding of a program with podSecurity exclusions
   DevBuf ctr_off, vol_off, sys_off, pann_off, c_name, c_image, c_sann_key, c_sec_str, c_pm_str, c_selt_str, c_selu_str,
       c_selr_str, cport_off, cport_str, pann_k, pann_v, p_cold;

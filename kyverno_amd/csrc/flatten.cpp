@@ -1586,7 +1586,195 @@ void load_ns_labels(Corpus& C, const char* js, size_t len) {
   if (!c.ok()) throw std::invalid_argument("malformed ns_labels_json");
 }
 
+// ---- the label table of a corpus that is already flattened (kpe_corpus_set_namespace_labels) ----
+// One table row while it is edited: its labels as dictionary ids (a row the table holds) or as
+// strings (a row of the JSON, interned only at the commit). `named` is false for a row no name
+// points to: the earlier occurrence of a key that occurs twice (load_ns_labels leaves one).
+struct NslRow {
+  std::string ns;
+  bool named = true, fresh = false, remove = false;
+  std::vector<std::pair<uint32_t, uint32_t>> ids;
+  std::vector<std::pair<std::string, std::string>> strs;
+};
+
+// the members of the JSON in order, read as load_ns_labels reads them; `null_removes`: the patch form
+std::vector<NslRow> parse_ns_rows(const char* js, size_t len, bool null_removes) {
+  std::vector<NslRow> out;
+  if (!js || !len) return out;
+  JCur c(js, js + len);
+  if (c.peek() == JK::Null) return out;
+  if (!c.obj_begin()) throw std::invalid_argument("ns_labels_json must be an object");
+  bool f = true;
+  std::string_view k;
+  std::string ks, vs;
+  while (c.obj_next(f, &k, ks)) {
+    NslRow row;
+    row.ns = std::string(k);
+    row.fresh = true;
+    if (c.peek() == JK::Obj) {
+      c.obj_begin();
+      bool f2 = true;
+      std::string_view k2;
+      std::string ks2;
+      while (c.obj_next(f2, &k2, ks2)) {
+        std::string lk(k2);
+        if (c.peek() == JK::Str) {
+          std::string_view v;
+          c.str(&v, vs);
+          row.strs.emplace_back(std::move(lk), std::string(v));
+        } else {
+          c.skip();
+        }
+      }
+    } else {
+      row.remove = null_removes && c.peek() == JK::Null;
+      c.skip();
+    }
+    out.push_back(std::move(row));
+  }
+  if (!c.ok()) throw std::invalid_argument("malformed ns_labels_json");
+  std::unordered_map<std::string, size_t> last;  // a key that occurs twice counts by its last occurrence
+  for (size_t i = 0; i < out.size(); ++i) last[out[i].ns] = i;
+  for (size_t i = 0; i < out.size(); ++i) out[i].named = last[out[i].ns] == i;
+  return out;
+}
+
+// a row's labels as a sorted set of id pairs; false when a string of it is in no dictionary (the
+// row then equals no row of the table)
+bool nsl_pair_set(const Corpus& C, const NslRow& r, std::vector<std::pair<uint32_t, uint32_t>>& out) {
+  out = r.ids;
+  for (const auto& kv : r.strs) {
+    const int64_t k = C.dict[D_LABK].find(kv.first), v = C.dict[D_LABV].find(kv.second);
+    if (k < 0 || v < 0) return false;
+    out.emplace_back((uint32_t)k, (uint32_t)v);
+  }
+  std::sort(out.begin(), out.end());
+  out.erase(std::unique(out.begin(), out.end()), out.end());
+  return true;
+}
+
 }  // namespace
+
+// Replace (replace) or patch the namespace label table of a flattened corpus from JSON read as
+// load_ns_labels reads it; in the patch form a member "<namespace>": null removes that entry.
+// Returns the number of namespaces whose entry changed (labels compared as sets of pairs); 0 leaves
+// the corpus untouched. Otherwise nsl_off / nsl_k / nsl_v / nsl_index are rebuilt (new strings
+// interned into D_LABK / D_LABV, behind every id in use), r_nsl is recomputed from r_nsa, and
+// group_map (when not null) receives the D_NS id -> table row map the device form of that
+// recomputation reads: dict[D_NS].size() + 1 entries, the last one KPE_NO_STR. D_NS is not touched.
+// Throws std::invalid_argument for malformed JSON, before anything changes.
+uint64_t set_ns_labels(Corpus& C, const char* js, size_t len, bool replace, std::vector<uint32_t>* group_map) {
+  std::vector<NslRow> in = parse_ns_rows(js, len, !replace);
+  if (in.empty() && !replace) return 0;
+  // the table as it is, in table order
+  const size_t nrows = C.nsl_off.size() - 1;
+  std::vector<NslRow> cur(nrows);
+  for (auto& r : cur) r.named = false;
+  for (const auto& kv : C.nsl_index)
+    if (kv.second < nrows) cur[kv.second].ns = kv.first, cur[kv.second].named = true;
+  for (size_t i = 0; i < nrows; ++i)
+    for (uint32_t j = C.nsl_off[i]; j < C.nsl_off[i + 1]; ++j) cur[i].ids.emplace_back(C.nsl_k[j], C.nsl_v[j]);
+  std::vector<std::pair<uint32_t, uint32_t>> a, b;
+  auto same = [&](const NslRow& x, const NslRow& y) {
+    const bool fx = nsl_pair_set(C, x, a), fy = nsl_pair_set(C, y, b);
+    return fx && fy && a == b;
+  };
+  uint64_t changed = 0;
+  std::vector<NslRow> next;
+  if (replace) {
+    std::unordered_map<std::string, size_t> now;
+    for (size_t i = 0; i < in.size(); ++i)
+      if (in[i].named) now[in[i].ns] = i;
+    for (const auto& r : cur)
+      if (r.named && !now.count(r.ns)) ++changed;
+    for (const auto& r : in) {
+      if (!r.named) continue;
+      auto it = C.nsl_index.find(r.ns);
+      if (it == C.nsl_index.end() || !same(cur[it->second], r)) ++changed;
+    }
+    next = std::move(in);
+  } else {
+    std::vector<bool> drop(nrows, false);
+    std::vector<NslRow> added;
+    for (auto& r : in) {
+      if (!r.named) continue;
+      auto it = C.nsl_index.find(r.ns);
+      if (r.remove) {
+        if (it != C.nsl_index.end()) drop[it->second] = true, ++changed;
+      } else if (it == C.nsl_index.end()) {
+        added.push_back(std::move(r)), ++changed;
+      } else if (!same(cur[it->second], r)) {
+        cur[it->second] = std::move(r), ++changed;
+      }
+    }
+    for (size_t i = 0; i < nrows; ++i)
+      if (cur[i].named && !drop[i]) next.push_back(std::move(cur[i]));
+    for (auto& r : added) next.push_back(std::move(r));
+  }
+  if (!changed) return 0;
+  // ---- commit ----
+  C.nsl_off.assign(1, 0u);
+  C.nsl_k.clear(), C.nsl_v.clear(), C.nsl_index.clear();
+  for (const auto& r : next) {
+    for (const auto& kv : r.ids) C.nsl_k.push_back(kv.first), C.nsl_v.push_back(kv.second);
+    for (const auto& kv : r.strs) {
+      C.nsl_k.push_back(C.dict[D_LABK].intern(kv.first));
+      C.nsl_v.push_back(C.dict[D_LABV].intern(kv.second));
+    }
+    if (r.named) C.nsl_index[r.ns] = (uint32_t)(C.nsl_off.size() - 1);
+    C.nsl_off.push_back((uint32_t)C.nsl_k.size());
+  }
+  const Dict& nsd = C.dict[D_NS];
+  std::vector<uint32_t> local;
+  std::vector<uint32_t>& map = group_map ? *group_map : local;
+  map.assign((size_t)nsd.size() + 1, KPE_NO_STR);
+  if (!C.nsl_index.empty())
+    for (uint32_t g = 0; g < nsd.size(); ++g) {
+      auto it = C.nsl_index.find(std::string(nsd.at(g)));
+      if (it != C.nsl_index.end()) map[g] = it->second;
+    }
+  for (size_t i = 0; i < C.r_nsl.size(); ++i) C.r_nsl[i] = map[std::min<uint32_t>(C.r_nsa[i], nsd.size())];
+  return changed;
+}
+
+// a JSON string: the bytes as they are, with the escapes a parser needs
+static void nsl_json_str(std::string& o, std::string_view s) {
+  static const char* hx = "0123456789abcdef";
+  o += '"';
+  for (unsigned char ch : s) {
+    if (ch == '"' || ch == '\\') o += '\\', o += (char)ch;
+    else if (ch < 0x20) o += "\\u00", o += hx[ch >> 4], o += hx[ch & 15];
+    else o += (char)ch;
+  }
+  o += '"';
+}
+
+// The table as JSON, {"<namespace>": {"<key>": "<value>", ...}, ...} in table order: what
+// set_ns_labels' replace form (and a flatten) reads back into the same table.
+std::string ns_labels_json(const Corpus& C) {
+  const size_t nrows = C.nsl_off.size() - 1;
+  std::vector<const std::string*> names(nrows, nullptr);
+  for (const auto& kv : C.nsl_index)
+    if (kv.second < nrows) names[kv.second] = &kv.first;
+  std::string out = "{";
+  bool first = true;
+  for (size_t i = 0; i < nrows; ++i) {
+    if (!names[i]) continue;
+    if (!first) out += ',';
+    first = false;
+    nsl_json_str(out, *names[i]);
+    out += ":{";
+    for (uint32_t j = C.nsl_off[i]; j < C.nsl_off[i + 1]; ++j) {
+      if (j > C.nsl_off[i]) out += ',';
+      nsl_json_str(out, C.dict[D_LABK].at(C.nsl_k[j]));
+      out += ':';
+      nsl_json_str(out, C.dict[D_LABV].at(C.nsl_v[j]));
+    }
+    out += '}';
+  }
+  out += '}';
+  return out;
+}
 
 bool typed_pod_view(const char* json, size_t len, PodView* out, std::string* kind) {
   Corpus scratch;
@@ -1607,6 +1795,7 @@ int64_t Corpus::bytes() const {
   int64_t b = 0;
   auto add = [&](const auto& v) { b += (int64_t)(v.size() * sizeof(v[0])); };
   add(r_flags), add(r_gvk), add(r_name), add(r_mns), add(r_nsa), add(r_nsl);
+  add(nsl_off), add(nsl_k), add(nsl_v);
   add(lab_off), add(lab_k), add(lab_v), add(ann_off), add(ann_k), add(ann_v);
   add(rec), add(hdr), add(crec), add(vol_src), add(sys_id), add(pann_kv), add(capset_add), add(capset_drop);
   add(c_sann);

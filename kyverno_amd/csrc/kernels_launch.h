@@ -122,4 +122,10 @@ hipError_t kpe_launch_report_need_scatter(const uint8_t* v, uint64_t cells, uint
 // its rule is a validate.foreach rule with a slot, zeros otherwise (slot: KPE_RR_SLOT per rule)
 hipError_t kpe_launch_fe_words_gather(const uint64_t* cells, uint64_t n, uint32_t R, const uint32_t* slot,
                                       const uint32_t* mtrace, uint32_t nmsg, uint32_t* out, hipStream_t s);
+
+// relabel.hip
+// kpe_corpus_set_namespace_labels: r_nsl[i] = map[min(r_nsa[i], G)] for the n rows; map has G + 1
+// entries (namespace id -> row of the new label table), map[G] = KPE_NO_STR
+hipError_t kpe_launch_nsl_remap(const uint32_t* r_nsa, const uint32_t* map, uint32_t G, uint64_t n, uint32_t* r_nsl,
+                                hipStream_t s);
 }

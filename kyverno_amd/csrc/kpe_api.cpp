@@ -30,6 +30,8 @@
 namespace kpe {
 void flatten_ndjson(Corpus& C, const char* buf, size_t len, const char* nsl, size_t nsl_len, bool docs);
 bool is_limit_error(const std::exception& e);
+uint64_t set_ns_labels(Corpus& C, const char* js, size_t len, bool replace, std::vector<uint32_t>* group_map);
+std::string ns_labels_json(const Corpus& C);
 }  // namespace kpe
 
 using kpe::DevBuf;
@@ -1867,6 +1869,70 @@ int64_t kpe_corpus_retired_rows(const kpe_corpus* c, uint64_t* rows, uint64_t ca
   const uint64_t m = std::min<uint64_t>(c->retired.size(), cap);
   for (uint64_t i = 0; i < m; ++i) rows[i] = c->retired[i];
   return (int64_t)c->retired.size();
+}
+
+kpe_status kpe_corpus_set_namespace_labels(kpe_device* dev, kpe_corpus* c, const char* js, size_t len, uint32_t flags,
+                                           uint64_t* changed) {
+  if (!c) return fail(KPE_E_INVALID, "null argument");
+  if (flags & ~KPE_NSL_REPLACE) return fail(KPE_E_INVALID, "kpe_corpus_set_namespace_labels: unknown flag");
+  if (c->d && (!dev || dev->ordinal != c->d->ordinal))
+    return fail(KPE_E_STATE, "the corpus is uploaded: change its namespace labels on its own device");
+  kpe::Corpus& C = *c->c;
+  const uint32_t nk0 = C.dict[D_LABK].size(), nv0 = C.dict[D_LABV].size();
+  std::vector<uint32_t> map;
+  uint64_t n = 0;
+  try {  // parsed in full before anything changes; the host columns are no evaluation's input
+    n = kpe::set_ns_labels(C, js, len, (flags & KPE_NSL_REPLACE) != 0, &map);
+  } catch (const std::exception& e) {
+    return fail(KPE_E_INVALID, e.what());
+  }
+  if (changed) *changed = n;
+  if (!n || !c->d) return KPE_OK;  // not uploaded: the next upload sends the table
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  auto& D = *c->d;
+  auto& B = D.bind;
+  // Behind the corpus's last evaluation, which is waited for first: the buffers it reads are
+  // replaced (a grown one is freed). The binding goes with the table: its requirement masks, LDS
+  // layout and argument copies follow the table and the dictionary sizes, so the next evaluation
+  // binds in full. What belongs to the corpus (kept results and fingerprints, the retired list,
+  // the rows-by-namespace index) does not read the table and stays.
+  hipStream_t s = B.last ? B.last : dev->stream;
+  HIPCHK(hipStreamSynchronize(s));
+  B.prog = nullptr, B.cells = 0;
+  B.args_valid = B.inv_ready = B.pargs_valid = B.cargs_valid = B.xargs_valid = false;
+  const auto up = [dev](DevBuf& b, const auto& v, hipStream_t st) { return upload_staged(dev, b, v, st); };
+  if (C.dict[D_LABK].size() != nk0) {
+    HIPCHK(up(D.dict_bytes[D_LABK], C.dict[D_LABK].bytes, s));
+    HIPCHK(up(D.dict_off[D_LABK], C.dict[D_LABK].off, s));
+  }
+  if (C.dict[D_LABV].size() != nv0) {
+    HIPCHK(up(D.dict_bytes[D_LABV], C.dict[D_LABV].bytes, s));
+    HIPCHK(up(D.dict_off[D_LABV], C.dict[D_LABV].off, s));
+  }
+  HIPCHK(up(D.nsl_off, C.nsl_off, s));
+  HIPCHK(up(D.nsl_k, C.nsl_k, s));
+  HIPCHK(up(D.nsl_v, C.nsl_v, s));
+  // r_nsl: rewritten where it is from the resident r_nsa through the namespace id -> table row map
+  // (4 bytes per namespace over the bus, not 4 per row). KPE_NSL_REUPLOAD=1 sends the host column
+  // instead, for A/B runs of the two (read at every call, so one process can alternate them).
+  const char* reupload = getenv("KPE_NSL_REUPLOAD");
+  if (reupload && atoi(reupload) != 0) {
+    HIPCHK(up(D.r_nsl, C.r_nsl, s));
+  } else {
+    HIPCHK(up(D.nsl_map, map, s));
+    HIPCHK(kpe_launch_nsl_remap(D.r_nsa.as<uint32_t>(), D.nsl_map.as<uint32_t>(), (uint32_t)map.size() - 1u, (uint64_t)C.n,
+                                D.r_nsl.as<uint32_t>(), s));
+  }
+  HIPCHK(hipStreamSynchronize(s));  // map and the staged copies are this call's
+  return KPE_OK;
+}
+
+int64_t kpe_corpus_namespace_labels(const kpe_corpus* c, char* out, size_t cap) {
+  if (!c || (cap && !out)) return -(int64_t)fail(KPE_E_INVALID, "null argument");
+  const std::string js = kpe::ns_labels_json(*c->c);
+  if (cap) memcpy(out, js.data(), std::min(cap, js.size()));
+  return (int64_t)js.size();
 }
 
 kpe_status kpe_evaluate_async(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c) {

@@ -202,6 +202,30 @@ class Corpus:
         check(load().kpe_corpus_namespace_rows(self.h, out.ctypes.data))
         return out
 
+    def namespace_labels(self) -> Dict[str, Dict[str, str]]:
+        """The namespace label table as it is now (kpe_corpus_namespace_labels), in table order:
+        what the constructor was given, after every Engine.set_namespace_labels since."""
+        L = load()
+        n = int(L.kpe_corpus_namespace_labels(self.h, None, 0))
+        if n < 0:
+            check(-n)
+        buf = ctypes.create_string_buffer(max(n, 1))
+        L.kpe_corpus_namespace_labels(self.h, buf, n)
+        return json.loads(buf.raw[:n].decode(errors="surrogateescape"))
+
+    def set_namespace_labels(self, labels, replace=False, device: Optional[Device] = None) -> int:
+        """Engine.set_namespace_labels on this corpus; device defaults to the one it is uploaded to
+        (none for a corpus that is not uploaded: the table then changes on the host alone)."""
+        js = bytes(labels) if isinstance(labels, (bytes, bytearray)) else (
+            b"" if labels is None else json.dumps(labels).encode())
+        dev = device if device is not None else self.device
+        n = ctypes.c_uint64(0)
+        check(load().kpe_corpus_set_namespace_labels(dev.h if dev is not None else None, self.h, js if js else None, len(js),
+                                                     NSL_REPLACE if replace else 0, ctypes.byref(n)))
+        if n.value:
+            self.nbytes = int(load().kpe_corpus_bytes(self.h))
+        return int(n.value)
+
     def upload(self, dev: Device):
         check(load().kpe_corpus_upload(dev.h, self.h))
         self.device = dev
@@ -581,6 +605,14 @@ class Engine:
         if n > 0:
             L.kpe_corpus_retired_rows(corpus.h, out.ctypes.data, n)
         return out
+
+    def set_namespace_labels(self, corpus: Corpus, labels, replace=False) -> int:
+        """Change the namespace label table of a flattened (and possibly uploaded, evaluated)
+        corpus in place (kpe_corpus_set_namespace_labels). labels: {namespace: {key: value}} or its
+        JSON bytes; a patch by default ({namespace: None} removes an entry, namespaces not named
+        keep theirs), with replace=True the whole table. Returns the number of namespaces whose
+        entry changed; when it is not 0 the corpus has no last evaluation until the next one."""
+        return corpus.set_namespace_labels(labels, replace, device=self.device if corpus.device is not None else None)
 
     @staticmethod
     def _pairs(pairs):
@@ -1031,6 +1063,7 @@ def delta_transitions(old, new, column_map) -> np.ndarray:
 
 
 FP_MASKS = 1  # include/kpe.h KPE_FP_MASKS: FAIL cells' check mask words count
+NSL_REPLACE = 1  # include/kpe.h KPE_NSL_REPLACE: the JSON is the whole namespace label table
 MESSAGE_CODES = SEL(2) | SEL(4) | SEL(5)  # FAIL, ERROR, SKIP: results whose message the policy text decides
 
 

@@ -71,6 +71,46 @@ def _key(row: bytes, i: int):
     return (d.get("apiVersion"), d.get("kind"), meta.get("namespace"), meta.get("name"))
 
 
+def namespace_label_events(upserts=(), deleted=()):
+    """The namespace label events among resource events (ResidentScanner(ns_objects=True)), as a
+    patch for set_namespace_labels: {name: labels, or None to remove the entry}. upserts: NDJSON
+    lines (or parsed resources); an `apiVersion: v1, kind: Namespace` object sets the entry of its
+    metadata.name to its string-valued metadata.labels. deleted: the deleted resources, as lines,
+    parsed resources or (apiVersion, kind, namespace, name) keys; a Namespace among them removes
+    its entry. Deletes count after upserts; a later event of a name replaces an earlier one. No
+    device, no library."""
+    def parsed(x):
+        if isinstance(x, (bytes, bytearray, str)):
+            try:
+                x = json.loads(x)
+            except ValueError:
+                return None
+        return x if isinstance(x, dict) else None
+
+    def ns_name(d):
+        if d is None or d.get("apiVersion") != "v1" or d.get("kind") != "Namespace":
+            return None
+        meta = d.get("metadata") if isinstance(d.get("metadata"), dict) else {}
+        name = meta.get("name")
+        return name if isinstance(name, str) and name else None
+
+    out = {}
+    for u in upserts:
+        d = parsed(u)
+        name = ns_name(d)
+        if name is not None:
+            labels = d["metadata"].get("labels")
+            out[name] = {k: v for k, v in labels.items() if isinstance(v, str)} if isinstance(labels, dict) else {}
+    for x in deleted:
+        if isinstance(x, tuple):
+            name = x[3] if len(x) == 4 and x[0] == "v1" and x[1] == "Namespace" and isinstance(x[3], str) and x[3] else None
+        else:
+            name = ns_name(parsed(x))
+        if name is not None:
+            out[name] = None
+    return out
+
+
 class RowMap:
     """Bookkeeping of a resident corpus under resource churn; no device, no library.
 
@@ -271,18 +311,27 @@ class ResidentScanner:
     With keyed=True the corpus also follows resource events (controller.go:247-297): `update`
     flattens only the resources whose hash changed into a delta segment, compares them on the device
     with the kept rows they replace and retires those rows where they were; the corpus, its upload
-    and its kept results stay. Rows are then logical rows (RowMap)."""
+    and its kept results stay. Rows are then logical rows (RowMap).
+
+    Namespace label changes (controller.go:310-318 reads the labels fresh at every rescan) are
+    applied in place too: `set_namespace_labels` replaces the label table of every segment on the
+    device and returns the rows whose report changes; with ns_objects=True `update` reads them off
+    the Namespace objects among its events."""
 
     MESSAGE_CODES = SEL(2) | SEL(4) | SEL(5)  # FAIL, ERROR, SKIP: results whose message the policy text decides
 
     def __init__(self, engine, ndjson: bytes, ns_labels=None, keep="matrix", fingerprints=None, edits=None,
-                 reports=False, keyed=False, max_segments=16, max_retired=0.25):
+                 reports=False, keyed=False, max_segments=16, max_retired=0.25, ns_objects=False):
         """keyed=True: the scanner also follows resource churn (`update`, `compact`, `matrix`). It
         then keeps the NDJSON lines, the resource-key index and the per-row resource hash
         (`resource_hashes`), and holds the corpus as segments (RowMap). `update` compacts past
         max_segments segments or once more than max_retired of the physical rows are retired; both
         defaults are unmeasured guesses (every segment adds launches to an `apply`, every retired
         row is scanned for nothing), not tuned values. Without keyed the class is what it was.
+
+        ns_objects=True (with keyed): `update` treats `apiVersion: v1, kind: Namespace` upserts and
+        deletes as label events of metadata.name (namespace_label_events) and applies them with
+        `set_namespace_labels` before it flattens the delta segment.
 
         reports=True: the scanner keeps the NDJSON lines and evaluates with check masks, so that
         `reports(rows)` can render the PolicyReport results of rows of the last applied PolicySet.
@@ -297,6 +346,8 @@ class ResidentScanner:
             raise ValueError('keep: "matrix" or "fingerprints"')
         if keep != "fingerprints" and (fingerprints is not None or edits is not None):
             raise ValueError('fingerprints, edits: only with keep="fingerprints"')
+        if ns_objects and not keyed:
+            raise ValueError("ns_objects: only with keyed=True")
         self.engine = engine
         self.keep = keep
         nsl = json.dumps(ns_labels).encode() if isinstance(ns_labels, dict) else ns_labels
@@ -305,6 +356,8 @@ class ResidentScanner:
         self._policies = None  # the PolicySet of the kept result (held while its matrix is kept)
         self._with_reports = bool(reports)
         self._keyed = bool(keyed)
+        self._ns_objects = bool(ns_objects)
+        self._stale = False  # keyed: rows were retired since the segments' last evaluation
         self._lines = ndjson_rows(ndjson) if (reports or keyed) else None  # logical row i is line i
         self._segs = [self.corpus]  # keyed: the segments (RowMap); segment 0 is self.corpus
         self._map = None
@@ -400,6 +453,77 @@ class ResidentScanner:
         self.last_stats = {"rows": corpus.n, "changed": total}
         return out
 
+    # ---- namespace label changes ----
+    def set_namespace_labels(self, labels, replace=False):
+        """The labels of namespaces changed (background/controller.go:310-318 reads them fresh at
+        every rescan): labels is {namespace: {key: value}, or None to remove the entry}, a patch by
+        default, the whole table with replace=True (Engine.set_namespace_labels). The table of every
+        segment is replaced in place, on the device; the corpus, its upload, the kept results and
+        the retired rows stay, and later delta segments and `compact` flatten with the new table.
+
+        With a PolicySet applied, returns {row: verdict row} of exactly the rows whose report
+        changes: the segments are evaluated again and compared with the kept result as `apply`
+        compares them with edited=() (keep="fingerprints": under the same message salts; `edits`
+        is untouched), and that result is then kept. {} before the first `apply`. When no entry
+        really changes nothing is done on the device."""
+        eng = self.engine
+        relabelled = max(eng.set_namespace_labels(seg, labels, replace) for seg in self._segs)
+        stats = {"relabelled": relabelled, "changed": 0}
+        out = {}
+        if relabelled:
+            self._nsl = json.dumps(self._segs[0].namespace_labels()).encode()
+            ps = self._applied
+            if ps is not None and self._keyed:
+                out = self._apply_segments(ps, np.zeros(ps.num_rules, dtype=np.uint8) if self._msg is None else None,
+                                           self._msg)
+                stats.update(rows=self.last_stats["rows"], segments=self.last_stats["segments"])
+            elif ps is not None:
+                stats["rows"] = self.corpus.n
+                eng.evaluate_async(ps, self.corpus, masks=self._with_reports)
+                if self.keep == "fingerprints":
+                    rows, vr, _, _ = eng.changed_rows_fp(ps, self.corpus, msg_salts=self._msg, msg_codes=self.MESSAGE_CODES)
+                else:
+                    rows, vr, _ = eng.changed_rows(ps, self.corpus)
+                self._keep(self.corpus)
+                out = {int(i): vr[k].copy() for k, i in enumerate(rows)}
+            stats["changed"] = len(out)
+        self.last_stats = stats
+        return out
+
+    def _refresh(self):
+        """Evaluate the segments again when rows were retired since their last evaluation: a
+        retired row gives no response from the next evaluation on."""
+        if self._applied is None:
+            raise KpeError(5, "no apply yet")  # KPE_E_STATE
+        if self._stale:
+            self.engine.evaluate_batch_async(self._applied, self._segs, masks=self._with_reports)
+            self._stale = False
+
+    def namespace_counts(self):
+        """Per-namespace rule counts of the resident corpus under the last applied PolicySet:
+        (names, (G, R, 6) uint64 counts, last axis NS_COUNT_FIELDS). Every segment's table is
+        reduced on its device (Engine.namespace_counts) and the tables are merged by namespace name
+        on the host (shard.merge_namespace_counts: a delta segment has few groups). Retired rows
+        give no response and count nowhere."""
+        from .shard import merge_namespace_counts
+
+        self._refresh()
+        return merge_namespace_counts([(seg.namespaces, self.engine.namespace_counts(self._applied, seg))
+                                       for seg in self._segs])
+
+    def cli_summary(self, audit_warn=False):
+        """`kyverno apply` totals of the resident corpus under the last applied PolicySet, the
+        action resolved per namespace from the current labels (cli_summary_ns per segment, summed)."""
+        from .engine import cli_summary_ns
+
+        self._refresh()
+        out = {"pass": 0, "fail": 0, "warn": 0, "error": 0, "skip": 0}
+        for seg in self._segs:
+            t = cli_summary_ns(self._applied, seg, self.engine.namespace_counts(self._applied, seg), audit_warn)
+            for k in out:
+                out[k] += t[k]
+        return out
+
     def reports(self, rows):
         """{row: PolicyReport results} of the listed rows under the last applied PolicySet, with
         messages (Engine.report_rows: one sparse fetch of what the rows' entries need, one bulk
@@ -431,6 +555,7 @@ class ResidentScanner:
         eng, m = self.engine, self._map
         eng.evaluate_batch_async(policies, self._segs, masks=self._with_reports)
         self._applied = policies
+        self._stale = False
         out = {}
         for s, seg in enumerate(self._segs):
             if msg is not None:
@@ -478,7 +603,17 @@ class ResidentScanner:
         self._need_keyed()
         eng, m = self.engine, self._map
         lines = ndjson_rows(upserts)
-        offered = list(zip((_key(r, i) for i, r in enumerate(lines)), resource_hashes(b"\n".join(lines)))) if lines else []
+        deletes = list(deletes)
+        relabel, relabelled = {}, 0
+        if self._ns_objects:
+            # a deleted resource is known by its stored line (a UID key says nothing of its kind), or
+            # by its key alone when the corpus never held it
+            gone = [d if m.row_of(d) is None else self._lines[m.row_of(d)] for d in deletes]
+            events = namespace_label_events(lines, [g for g in gone if g is not None])
+            if events:  # before the delta segment is flattened: it takes the new table
+                relabel = self.set_namespace_labels(events)
+                relabelled = self.last_stats["relabelled"]
+        offered =list(zip((_key(r, i) for i, r in enumerate(lines)), resource_hashes(b"\n".join(lines)))) if lines else []
         plan = m.plan(offered, deletes)
         items = plan["items"]
         out = {}
@@ -524,9 +659,14 @@ class ResidentScanner:
             self._lines[l] = None
         for s, rr in retire.items():
             eng.retire_rows(self._segs[s], rr)
+            self._stale = True
         self._updated = True
+        if relabel:  # the rows the label events changed; a row in both is what the update made of it
+            out = {**relabel, **out}
         self.last_stats = {"rows": m.n_live, "offered": len(lines), "skipped": plan["skipped"], "rescanned": len(items),
                            "deleted": len(plan["deletes"]), "changed": len(out), "segments": len(self._segs)}
+        if self._ns_objects:
+            self.last_stats["relabelled"] = relabelled
         if m.needs_compaction():
             self.compact()
             self.last_stats["segments"] = len(self._segs)
@@ -548,6 +688,7 @@ class ResidentScanner:
             raise KpeError(2, "compact: one corpus row per live resource")  # KPE_E_INVALID
         self._segs = [seg]
         self.corpus = seg
+        self._stale = False
         if self._applied is not None:
             eng.evaluate_async(self._applied, seg, masks=self._with_reports)
             if self.keep != "fingerprints":

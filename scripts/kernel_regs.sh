@@ -4,7 +4,7 @@
 set -e
 T=$(mktemp -d)
 K=kyverno_amd/build
-for O in ${@:-$K/scan.o $K/results.o $K/pssx.o $K/pattern.o $K/pattern_trace.o $K/cond.o $K/cond_fepat.o}; do
+for O in ${@:-$K/scan.o $K/results.o $K/pssx.o $K/relabel.o $K/pattern.o $K/pattern_trace.o $K/cond.o $K/cond_fepat.o}; do
 B=/opt/rocm/lib/llvm/bin
 $B/llvm-objcopy --dump-section=.hip_fatbin=$T/fb.bin "$O"
 $B/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$T/fb.bin --output=$T/k.co --unbundle
