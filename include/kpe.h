@@ -413,6 +413,74 @@ int64_t kpe_changed_rows_host(const uint8_t* old_v, const uint8_t* new_v, uint64
 kpe_status kpe_delta_transitions_host(const uint8_t* old_v, const uint8_t* new_v, uint64_t n, uint32_t Ro, uint32_t Rn,
                                       const int32_t* old_of, uint64_t* out);
 
+/* ---- policy edits on a kept result -------------------------------------------- */
+/* One policy edited, added or removed out of hundreds. After a policy change the background
+ * controller keeps the stored results of the unchanged policies and recomputes only the changed ones
+ * (pkg/controllers/report/background/controller.go:379-419). A rule's verdict depends only on its
+ * own policy, the resource, the namespace labels and the exceptions naming that policy, so the
+ * columns of a policy compiled alone equal its columns inside the full program: evaluate `sub`, the
+ * edited and added policies compiled alone with their exceptions, and splice its N x Rs matrix E
+ * into the kept matrix K (N x Ro) instead of evaluating, comparing and keeping all R columns.
+ *
+ * The plan. Names are "<policy>/<rule>". The new kept matrix K' (N x rn) is the kept columns in
+ * order, where a column whose policy is neither in sub nor in `removed` is copied (plan[r] = c); at
+ * the first kept column of a policy sub holds, all of sub's columns of that policy follow in sub's
+ * order (plan[r] = -1 - s) and the policy's other kept columns are skipped, so an edited policy
+ * keeps its place whatever its rule count; the columns of removed policies vanish; the policies of
+ * sub not among the kept ones are appended in sub's order. K' takes the kept names of copied columns
+ * and kpe_program_rule_name(sub, s) for the others. kpe_splice_plan writes the first min(rn, cap)
+ * entries and returns rn, or -kpe_status: KPE_E_INVALID for a null argument, a removed name that sub
+ * also holds, or a rule name that occurs twice on either side; KPE_E_STATE when nothing is kept;
+ * KPE_E_LIMIT when Ro, Rs or rn is past KPE_DELTA_MAX_RULES. Host only. kpe_splice_plan_names is
+ * the same over two name lists (no corpus, no rule limit) and also gives partner[s], the kept
+ * column named like column s of sub, or -1 (NULL: not wanted). */
+int64_t kpe_splice_plan(const kpe_corpus* c, const kpe_program* sub, const char* const* removed, uint32_t nremoved,
+                        int32_t* plan, uint32_t cap);
+int64_t kpe_splice_plan_names(const char* const* kept, uint32_t Ro, const char* const* sub, uint32_t Rs,
+                              const char* const* removed, uint32_t nremoved, int32_t* plan, int32_t* partner,
+                              uint32_t cap);
+/* kpe_results_splice: the corpus holds a kept result and its last evaluation is of sub (KPE_E_STATE
+ * otherwise, or when it is uploaded to another device; a sub without rules, for an edit that only
+ * removes policies, needs no evaluation). One kernel pass, enqueued behind that
+ * evaluation and ahead of the corpus's next one on the stream kpe_results_keep uses, writes K' into a
+ * second buffer the corpus owns and one flag byte per row; then the two buffers swap and the kept R
+ * and names become K''s: kpe_results_kept_rule_name, kpe_delta_column_map, kpe_changed_rows and
+ * kpe_changed_pairs see K' like any kept result. Row i is changed (the rule of kpe_changed_rows
+ * between K and K', restricted to what can differ; copied columns are equal by construction) iff
+ *   - E[i][s] != K[i][p(s)] for some column s of sub, p(s) the kept column of the same name (none:
+ *     the cell counts as KPE_NA), or
+ *   - (always[s] >> E[i][s]) & 1 for some column s of sub (always: Rs bytes, NULL = all zero), or
+ *   - a kept column that is neither copied nor a partner holds a code other than KPE_NA in row i.
+ * Returns the number of changed rows (the call waits for the pass), or -kpe_status: the plan's
+ * errors, checked before any device call. The old buffer stays as the spare of the next splice and
+ * the flags (N bytes) stay until the next splice, keep, drop or upload: a corpus that splices costs
+ * up to 2 x N x max(Ro, rn) + N bytes of device memory; kpe_results_drop, kpe_corpus_upload and
+ * kpe_corpus_free release all of it. Check masks and traces are not kept across a splice. */
+int64_t kpe_results_splice(kpe_device* dev, const kpe_program* sub, kpe_corpus* c, const char* const* removed,
+                           uint32_t nremoved, const uint8_t* always /* Rs bytes or NULL */);
+/* The changed rows of the last kpe_results_splice on the corpus (KPE_E_STATE without one): the first
+ * min(total, cap) row indices, ascending, into rows[] and, when verdict_rows is not NULL, those rows
+ * of K' (rn bytes each); memory past that is not written. rows == NULL with cap == 0 counts only.
+ * Reads the kept flag bytes; compares nothing again, and may be called repeatedly. Returns the total
+ * or -kpe_status. */
+int64_t kpe_spliced_rows(kpe_device* dev, const kpe_corpus* c, uint64_t* rows, uint8_t* verdict_rows, uint64_t cap);
+/* The same over matrices the caller holds (kept: n x Ro, sub_v: n x Rs; plan: rn entries; partner:
+ * Rs entries, -1 = none; always: Rs bytes or NULL): writes out (n x rn) and flags (n bytes of 0 / 1)
+ * and returns the number of changed rows, or -KPE_E_INVALID for a null argument, an entry out of
+ * range, a kept column copied or partnered twice or both, or a column of sub emitted twice or not at
+ * all. The specification of kpe_results_splice. No rule limit. Host only; no device call. */
+int64_t kpe_results_splice_host(const uint8_t* kept, const uint8_t* sub_v, uint64_t n, uint32_t Ro, uint32_t Rs,
+                                uint32_t rn, const int32_t* plan, const int32_t* partner, const uint8_t* always,
+                                uint8_t* out, uint8_t* flags);
+/* Rows [row0, row0 + nrows) of the kept matrix (kept R bytes each) to the host: diagnostics and
+ * tests. KPE_E_STATE when nothing is kept. */
+kpe_status kpe_results_kept_fetch(kpe_device* dev, const kpe_corpus* c, uint64_t row0, uint64_t nrows, uint8_t* out);
+/* The splice pass: its algorithmic bytes, N x (Ro + Rs + rn + 1); the rows of one of its row groups
+ * and the most groups in flight (blocks of its persistent grid). */
+double kpe_splice_bytes(uint64_t n, uint32_t Ro, uint32_t Rs, uint32_t rn);
+uint32_t kpe_splice_group_rows(uint32_t Ro, uint32_t Rs, uint32_t rn);
+uint32_t kpe_splice_max_groups(void);
+
 /* ---- row fingerprints -------------------------------------------------------- */
 /* Report-change detection in 8 bytes per resource. The reference decides "identical or not" from one
  * small thing per report (ReportsAreIdentical, pkg/controllers/report/utils/utils.go:66-88) and stores

@@ -108,6 +108,23 @@ def load():
     L.kpe_changed_rows_host.restype = i64
     L.kpe_delta_transitions_host.argtypes = [vp, vp, u64, u32, u32, vp, vp]
     L.kpe_delta_transitions_host.restype = ctypes.c_int
+    L.kpe_splice_plan.argtypes = [vp, vp, vp, u32, vp, u32]
+    L.kpe_splice_plan.restype = i64
+    L.kpe_splice_plan_names.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, u32]
+    L.kpe_splice_plan_names.restype = i64
+    L.kpe_results_splice.argtypes = [vp, vp, vp, vp, u32, vp]
+    L.kpe_results_splice.restype = i64
+    L.kpe_spliced_rows.argtypes = [vp, vp, vp, vp, u64]
+    L.kpe_spliced_rows.restype = i64
+    L.kpe_results_splice_host.argtypes = [vp, vp, u64, u32, u32, u32, vp, vp, vp, vp, vp]
+    L.kpe_results_splice_host.restype = i64
+    L.kpe_results_kept_fetch.argtypes = [vp, vp, u64, u64, vp]
+    L.kpe_results_kept_fetch.restype = ctypes.c_int
+    L.kpe_splice_bytes.argtypes = [u64, u32, u32, u32]
+    L.kpe_splice_bytes.restype = ctypes.c_double
+    L.kpe_splice_group_rows.argtypes = [u32, u32, u32]
+    L.kpe_splice_group_rows.restype = u32
+    L.kpe_splice_max_groups.restype = u32
     u8 = ctypes.c_uint8
     L.kpe_fp_rule_salts.argtypes = [vp, vp]
     L.kpe_fp_rule_salts.restype = ctypes.c_int

@@ -324,6 +324,11 @@ struct DeviceCorpus {
   DevBuf kept;
   int64_t kept_rules = -1;  // -1: nothing kept
   std::vector<std::string> kept_names;
+  // kpe_results_splice: the second matrix buffer (K' is written there and the two swap, the old one
+  // stays as the spare of the next splice) and the row flags of the last splice (N bytes, valid
+  // until the next splice, keep, drop or upload; kpe_spliced_rows reads them)
+  DevBuf kept_spare, splice_flags;
+  bool splice_valid = false;
   // the kept fingerprints (kpe_fingerprints_keep / _load): 8 bytes per row, independent of `kept`
   DevBuf fps;
   std::vector<uint64_t> fps_tbl;  // host bytes of the last keep's salt table (its copy is enqueued)

@@ -153,6 +153,7 @@ kpe_status kpe_results_keep(kpe_device* dev, const kpe_program* prog, kpe_corpus
   const size_t R = P.rules.size();
   const size_t cells = (size_t)c->c->n * R;
   D.kept_rules = -1;
+  D.splice_valid = false;
   HIPCHK(D.kept.ensure(cells));
   // on the stream of the evaluation: after it, and before the corpus's next one (launch() keeps a
   // corpus's launches ordered and a rebind waits for B.last)
@@ -174,6 +175,11 @@ kpe_status kpe_results_drop(kpe_device* dev, kpe_corpus* c) {
   D.kept_names.clear();
   if (D.kept.p) HIPCHK(hipFree(D.kept.p));  // waits for the copy
   D.kept.p = nullptr, D.kept.bytes = 0;
+  D.splice_valid = false;
+  if (D.kept_spare.p) HIPCHK(hipFree(D.kept_spare.p));
+  D.kept_spare.p = nullptr, D.kept_spare.bytes = 0;
+  if (D.splice_flags.p) HIPCHK(hipFree(D.splice_flags.p));
+  D.splice_flags.p = nullptr, D.splice_flags.bytes = 0;
   return KPE_OK;
 }
 
@@ -507,6 +513,316 @@ kpe_status kpe_delta_transitions(kpe_device* dev, const kpe_program* prog, const
   HIPCHK(kpe_launch_delta_transitions(B.verdicts.as<uint8_t>(), D.kept.as<uint8_t>(), (uint64_t)c->c->n, (uint32_t)Rn,
                                       (uint32_t)Ro, d_tab, scratch.as<unsigned long long>(), s));
   HIPCHK(hipMemcpyAsync(out, scratch.p, out_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return KPE_OK;
+}
+
+// ---- policy edits on a kept result: the plan, the splice, its changed rows ---------------------
+namespace {
+std::string splice_policy_of(const std::string& name) { return name.substr(0, name.find('/')); }
+
+// The column plan of include/kpe.h over two name lists, and the partner (the kept column of the
+// same name, or -1) of every column of sub.
+kpe_status splice_plan_build(const std::vector<std::string>& kept, const std::vector<std::string>& sub,
+                             const char* const* removed, uint32_t nremoved, std::vector<int32_t>& plan,
+                             std::vector<int32_t>& partner) {
+  std::map<std::string, int32_t> kept_col, sub_col;
+  for (size_t r = 0; r < kept.size(); ++r)
+    if (!kept_col.emplace(kept[r], (int32_t)r).second) return fail(KPE_E_INVALID, "kept rule name occurs twice: " + kept[r]);
+  std::map<std::string, std::vector<int32_t>> by_policy;  // policy of sub -> its columns, in sub's order
+  std::vector<std::string> order;                         // sub's policies, by first column
+  for (size_t s = 0; s < sub.size(); ++s) {
+    if (!sub_col.emplace(sub[s], (int32_t)s).second) return fail(KPE_E_INVALID, "rule name occurs twice: " + sub[s]);
+    auto& cols = by_policy[splice_policy_of(sub[s])];
+    if (cols.empty()) order.push_back(splice_policy_of(sub[s]));
+    cols.push_back((int32_t)s);
+  }
+  std::map<std::string, bool> gone;
+  for (uint32_t k = 0; k < nremoved; ++k) {
+    if (!removed || !removed[k]) return fail(KPE_E_INVALID, "null argument");
+    if (by_policy.count(removed[k])) return fail(KPE_E_INVALID, std::string("removed policy is also edited: ") + removed[k]);
+    gone[removed[k]] = true;
+  }
+  plan.clear();
+  std::map<std::string, bool> emitted;
+  const auto emit = [&](const std::string& pol) {
+    for (int32_t s : by_policy[pol]) plan.push_back(-1 - s);
+    emitted[pol] = true;
+  };
+  for (size_t c = 0; c < kept.size(); ++c) {
+    const std::string pol = splice_policy_of(kept[c]);
+    if (by_policy.count(pol)) {
+      if (!emitted.count(pol)) emit(pol);  // an edited policy keeps its place
+    } else if (!gone.count(pol)) {
+      plan.push_back((int32_t)c);
+    }
+  }
+  for (const std::string& pol : order)
+    if (!emitted.count(pol)) emit(pol);  // added policies, at the end
+  partner.resize(sub.size());
+  for (size_t s = 0; s < sub.size(); ++s) {
+    const auto it = kept_col.find(sub[s]);
+    partner[s] = it == kept_col.end() ? -1 : it->second;
+  }
+  return KPE_OK;
+}
+
+const char* const kSpliceLimit = "a splice takes at most 4096 rules on any side";
+kpe_status splice_limit(size_t Ro, size_t Rs, size_t rn) {
+  if (Ro > KPE_DELTA_MAX_RULES || Rs > KPE_DELTA_MAX_RULES || rn > KPE_DELTA_MAX_RULES) return fail(KPE_E_LIMIT, kSpliceLimit);
+  return KPE_OK;
+}
+std::vector<std::string> program_names(const kpe::Program& P) {
+  std::vector<std::string> names(P.rule_names.begin(), P.rule_names.end());
+  names.resize(P.rules.size());
+  return names;
+}
+
+// What the host twin and the device call check of a plan, and the tables the kernel reads (col,
+// unm: kernels_launch.h kpe_launch_splice).
+kpe_status splice_tables(const int32_t* plan, size_t rn, const int32_t* partner, size_t Rs, size_t Ro,
+                         const uint8_t* always, std::vector<uint32_t>& col, std::vector<uint8_t>& unm, bool* any_unm) {
+  std::vector<uint8_t> copied(Ro, 0), emitted(Rs, 0);
+  col.assign(2 * rn, 0);
+  unm.assign(Ro, 1);
+  for (size_t s = 0; s < Rs; ++s) {
+    const int32_t p = partner[s];
+    if (p == -1) continue;
+    if (p < -1 || (size_t)p >= Ro) return fail(KPE_E_INVALID, "partner outside the kept rules");
+    if (!unm[(size_t)p]) return fail(KPE_E_INVALID, "partner names a kept column twice");
+    unm[(size_t)p] = 0;
+  }
+  for (size_t r = 0; r < rn; ++r) {
+    const int32_t e = plan[r];
+    if (e >= 0) {
+      if ((size_t)e >= Ro) return fail(KPE_E_INVALID, "plan entry outside the kept rules");
+      if (copied[(size_t)e]) return fail(KPE_E_INVALID, "plan copies a kept column twice");
+      if (!unm[(size_t)e]) return fail(KPE_E_INVALID, "plan copies a partner column");
+      copied[(size_t)e] = 1;
+      col[2 * r] = (uint32_t)e;
+    } else {
+      const size_t s = (size_t)(-1 - (int64_t)e);
+      if (s >= Rs) return fail(KPE_E_INVALID, "plan entry outside the sub rules");
+      if (emitted[s]) return fail(KPE_E_INVALID, "plan emits a sub column twice");
+      emitted[s] = 1;
+      col[2 * r] = 0x80000000u | (uint32_t)s;
+      col[2 * r + 1] = (partner[s] < 0 ? 0xFFFFu : (uint32_t)partner[s]) | ((uint32_t)(always ? always[s] : 0) << 16);
+    }
+  }
+  for (size_t s = 0; s < Rs; ++s)
+    if (!emitted[s]) return fail(KPE_E_INVALID, "plan leaves a sub column out");
+  *any_unm = false;
+  for (size_t o = 0; o < Ro; ++o) {
+    if (copied[o]) unm[o] = 0;
+    *any_unm |= unm[o] != 0;
+  }
+  return KPE_OK;
+}
+}  // namespace
+
+int64_t kpe_splice_plan_names(const char* const* kept, uint32_t Ro, const char* const* sub, uint32_t Rs,
+                              const char* const* removed, uint32_t nremoved, int32_t* plan, int32_t* partner,
+                              uint32_t cap) {
+  if ((Ro && !kept) || (Rs && !sub) || (cap && !plan)) return -(int64_t)fail(KPE_E_INVALID, "null argument");
+  std::vector<std::string> kn(Ro), sn(Rs);
+  for (uint32_t r = 0; r < Ro; ++r) {
+    if (!kept[r]) return -(int64_t)fail(KPE_E_INVALID, "null argument");
+    kn[r] = kept[r];
+  }
+  for (uint32_t s = 0; s < Rs; ++s) {
+    if (!sub[s]) return -(int64_t)fail(KPE_E_INVALID, "null argument");
+    sn[s] = sub[s];
+  }
+  std::vector<int32_t> pl, pa;
+  if (kpe_status st = splice_plan_build(kn, sn, removed, nremoved, pl, pa)) return -(int64_t)st;
+  for (size_t r = 0; r < pl.size() && r < cap; ++r) plan[r] = pl[r];
+  if (partner)
+    for (uint32_t s = 0; s < Rs; ++s) partner[s] = pa[s];
+  return (int64_t)pl.size();
+}
+
+int64_t kpe_splice_plan(const kpe_corpus* c, const kpe_program* sub, const char* const* removed, uint32_t nremoved,
+                        int32_t* plan, uint32_t cap) {
+  if (!c || !sub || (cap && !plan)) return -(int64_t)fail(KPE_E_INVALID, "null argument");
+  if (!c->d || c->d->kept_rules < 0) return -(int64_t)fail(KPE_E_STATE, "no kept result on this corpus");
+  std::vector<int32_t> pl, pa;
+  if (kpe_status st = splice_plan_build(c->d->kept_names, program_names(*sub->p), removed, nremoved, pl, pa))
+    return -(int64_t)st;
+  if (kpe_status st = splice_limit(c->d->kept_names.size(), pa.size(), pl.size())) return -(int64_t)st;
+  for (size_t r = 0; r < pl.size() && r < cap; ++r) plan[r] = pl[r];
+  return (int64_t)pl.size();
+}
+
+int64_t kpe_results_splice_host(const uint8_t* kept, const uint8_t* sub_v, uint64_t n, uint32_t Ro, uint32_t Rs,
+                                uint32_t rn, const int32_t* plan, const int32_t* partner, const uint8_t* always,
+                                uint8_t* out, uint8_t* flags) {
+  if ((rn && !plan) || (Rs && !partner)) return -(int64_t)fail(KPE_E_INVALID, "null argument");
+  if (n && ((Ro && !kept) || (Rs && !sub_v) || (rn && !out) || !flags)) return -(int64_t)fail(KPE_E_INVALID, "null argument");
+  std::vector<uint32_t> col;
+  std::vector<uint8_t> unm;
+  bool any_unm = false;
+  if (kpe_status st = splice_tables(plan, rn, partner, Rs, Ro, always, col, unm, &any_unm)) return -(int64_t)st;
+  uint64_t total = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint8_t* k = kept + (size_t)i * Ro;
+    const uint8_t* e = sub_v + (size_t)i * Rs;
+    uint8_t* o = out + (size_t)i * rn;
+    for (uint32_t r = 0; r < rn; ++r) o[r] = plan[r] >= 0 ? k[plan[r]] : e[-1 - plan[r]];
+    bool ch = false;
+    for (uint32_t s = 0; s < Rs && !ch; ++s) {
+      const uint8_t x = e[s], p = partner[s] >= 0 ? k[partner[s]] : (uint8_t)KPE_NA;
+      ch = x != p || delta_always(always, s, x);
+    }
+    for (uint32_t c = 0; c < Ro && !ch && any_unm; ++c) ch = unm[c] && k[c] != KPE_NA;
+    flags[i] = ch ? 1 : 0;
+    total += ch;
+  }
+  return (int64_t)total;
+}
+
+double kpe_splice_bytes(uint64_t n, uint32_t Ro, uint32_t Rs, uint32_t rn) {
+  return (double)n * ((double)Ro + (double)Rs + (double)rn + 1.0);
+}
+uint32_t kpe_splice_group_rows(uint32_t Ro, uint32_t Rs, uint32_t rn) { return kpe_splice_rows_per_group(Ro, Rs, rn); }
+uint32_t kpe_splice_max_groups(void) { return kpe_splice_grid(); }
+
+static kpe_status splice_impl(kpe_device* dev, const kpe_program* sub, kpe_corpus* c, const char* const* removed,
+                              uint32_t nremoved, const uint8_t* always, uint64_t* total_out) {
+  *total_out = 0;
+  if (!dev || !sub || !c) return fail(KPE_E_INVALID, "null argument");
+  if (!c->d || c->d->kept_rules < 0) return fail(KPE_E_STATE, "no kept result on this corpus");
+  kpe::DeviceCorpus& D = *c->d;
+  const std::vector<std::string> sub_names = program_names(*sub->p);
+  std::vector<int32_t> plan, partner;
+  if (kpe_status st = splice_plan_build(D.kept_names, sub_names, removed, nremoved, plan, partner)) return st;
+  const size_t Ro = (size_t)D.kept_rules, Rs = sub_names.size(), rn = plan.size();
+  if (kpe_status st = splice_limit(Ro, Rs, rn)) return st;
+  std::vector<uint32_t> col;
+  std::vector<uint8_t> unm;
+  bool any_unm = false;
+  if (kpe_status st = splice_tables(plan.data(), rn, partner.data(), Rs, Ro, always, col, unm, &any_unm)) return st;
+  std::vector<std::string> names(rn);
+  for (size_t r = 0; r < rn; ++r) names[r] = plan[r] >= 0 ? D.kept_names[(size_t)plan[r]] : sub_names[(size_t)(-1 - plan[r])];
+  const uint64_t n = (uint64_t)c->c->n;
+  std::lock_guard<std::mutex> lk(dev->mu);
+  if (Rs) {
+    if (kpe_status st = delta_bound(dev, sub, c)) return st;
+  } else {  // only removals: there is no E to read, so no evaluation of sub is asked for
+    HIPCHK(hipSetDevice(dev->ordinal));
+    if (D.ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  }
+  auto& B = D.bind;
+  // on the stream of the evaluation of sub: after it, and before the corpus's next one
+  hipStream_t s = B.last ? B.last : dev->stream;
+  D.splice_valid = false;
+  uint64_t total = 0;
+  if (n) {
+    const uint64_t ntiles = (n + 4095u) / 4096u;
+    const size_t off_bytes = (size_t)((ntiles + 2) & ~(uint64_t)1) * 8;
+    const size_t cnt_bytes = (size_t)((ntiles + 3) & ~(uint64_t)3) * 4;
+    const size_t col_bytes = (col.size() * 4 + 15u) & ~(size_t)15u;
+    DevBuf scratch;  // this call's, freed on every return path: the selection's tiles, its mask, the tables
+    HIPCHK(scratch.ensure(off_bytes + cnt_bytes + col_bytes + 16 + Ro));
+    HIPCHK(D.kept_spare.ensure(n * std::max<size_t>(rn, 1)));
+    HIPCHK(D.splice_flags.ensure((size_t)((n + 15u) & ~(uint64_t)15u)));
+    uint8_t* base = scratch.as<uint8_t>();
+    uint64_t* d_off = reinterpret_cast<uint64_t*>(base);
+    uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + off_bytes);
+    uint32_t* d_col = reinterpret_cast<uint32_t*>(base + off_bytes + cnt_bytes);
+    uint8_t* d_sel = base + off_bytes + cnt_bytes + col_bytes;
+    uint8_t* d_unm = d_sel + 16;
+    const uint8_t sel1 = (uint8_t)KPE_SEL(1);
+    if (rn) HIPCHK(hipMemcpyAsync(d_col, col.data(), col.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_sel, &sel1, 1, hipMemcpyHostToDevice, s));
+    if (any_unm) HIPCHK(hipMemcpyAsync(d_unm, unm.data(), Ro, hipMemcpyHostToDevice, s));
+    HIPCHK(kpe_launch_splice(D.kept.as<uint8_t>(), B.verdicts.as<uint8_t>(), n, (uint32_t)Ro, (uint32_t)Rs, (uint32_t)rn,
+                             d_col, any_unm ? d_unm : nullptr, D.kept_spare.as<uint8_t>(), D.splice_flags.as<uint8_t>(), s));
+    HIPCHK(kpe_launch_select_count(D.splice_flags.as<uint8_t>(), n, 1u, d_sel, 0, d_cnt, d_off, s));
+    HIPCHK(hipMemcpyAsync(&total, d_off + ntiles, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::swap(D.kept.p, D.kept_spare.p);
+    std::swap(D.kept.bytes, D.kept_spare.bytes);
+  }
+  D.kept_names.swap(names);
+  D.kept_rules = (int64_t)rn;
+  D.splice_valid = true;
+  *total_out = total;
+  return KPE_OK;
+}
+
+int64_t kpe_results_splice(kpe_device* dev, const kpe_program* sub, kpe_corpus* c, const char* const* removed,
+                           uint32_t nremoved, const uint8_t* always) {
+  uint64_t total = 0;
+  const kpe_status st = splice_impl(dev, sub, c, removed, nremoved, always, &total);
+  return st ? -(int64_t)st : (int64_t)total;
+}
+
+static kpe_status spliced_impl(kpe_device* dev, const kpe_corpus* c, uint64_t* rows_out, uint8_t* vrows_out, uint64_t cap,
+                               uint64_t* total_out) {
+  *total_out = 0;
+  if (!dev || !c) return fail(KPE_E_INVALID, "null argument");
+  if (cap && !rows_out) return fail(KPE_E_INVALID, "cap > 0 without a rows buffer");
+  if (!c->d || c->d->kept_rules < 0 || !c->d->splice_valid) return fail(KPE_E_STATE, "no splice on this corpus");
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  kpe::DeviceCorpus& D = *c->d;
+  if (D.ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  const uint64_t n = (uint64_t)c->c->n;
+  const size_t rn = (size_t)D.kept_rules;
+  if (!n) return KPE_OK;
+  hipStream_t s = D.bind.last ? D.bind.last : dev->stream;
+  const uint64_t ntiles = (n + 4095u) / 4096u;
+  const size_t off_bytes = (size_t)((ntiles + 2) & ~(uint64_t)1) * 8;
+  const size_t cnt_bytes = (size_t)((ntiles + 3) & ~(uint64_t)3) * 4;
+  DevBuf scratch, drows, dverd;
+  HIPCHK(scratch.ensure(off_bytes + cnt_bytes + 16));
+  uint8_t* base = scratch.as<uint8_t>();
+  uint64_t* d_off = reinterpret_cast<uint64_t*>(base);
+  uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + off_bytes);
+  uint8_t* d_sel = base + off_bytes + cnt_bytes;
+  const uint8_t* d_flags = D.splice_flags.as<uint8_t>();
+  const uint8_t sel1 = (uint8_t)KPE_SEL(1);
+  HIPCHK(hipMemcpyAsync(d_sel, &sel1, 1, hipMemcpyHostToDevice, s));
+  HIPCHK(kpe_launch_select_count(d_flags, n, 1u, d_sel, 0, d_cnt, d_off, s));
+  uint64_t total = 0;
+  HIPCHK(hipMemcpyAsync(&total, d_off + ntiles, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *total_out = total;
+  const uint64_t m = std::min(total, cap);
+  if (!m) return KPE_OK;
+  HIPCHK(drows.ensure((size_t)m * 8));
+  HIPCHK(kpe_launch_select_scatter(d_flags, n, 1u, d_sel, 0, d_off, m, drows.as<uint64_t>(), nullptr, s));
+  const bool vr = vrows_out && rn;
+  if (vr) {
+    HIPCHK(dverd.ensure((size_t)m * rn));
+    HIPCHK(kpe_launch_gather_rows(D.kept.as<uint8_t>(), (uint32_t)rn, drows.as<uint64_t>(), m, dverd.as<uint8_t>(), s));
+  }
+  HIPCHK(hipMemcpyAsync(rows_out, drows.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+  if (vr) HIPCHK(hipMemcpyAsync(vrows_out, dverd.p, (size_t)m * rn, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return KPE_OK;
+}
+
+int64_t kpe_spliced_rows(kpe_device* dev, const kpe_corpus* c, uint64_t* rows, uint8_t* verdict_rows, uint64_t cap) {
+  uint64_t total = 0;
+  const kpe_status st = spliced_impl(dev, c, rows, verdict_rows, cap, &total);
+  return st ? -(int64_t)st : (int64_t)total;
+}
+
+kpe_status kpe_results_kept_fetch(kpe_device* dev, const kpe_corpus* c, uint64_t row0, uint64_t nrows, uint8_t* out) {
+  if (!dev || !c) return fail(KPE_E_INVALID, "null argument");
+  if (!c->d || c->d->kept_rules < 0) return fail(KPE_E_STATE, "no kept result on this corpus");
+  const uint64_t n = (uint64_t)c->c->n;
+  if (row0 > n || nrows > n - row0) return fail(KPE_E_INVALID, "rows past the corpus");
+  const size_t R = (size_t)c->d->kept_rules;
+  if (!nrows || !R) return KPE_OK;
+  if (!out) return fail(KPE_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(dev->mu);
+  HIPCHK(hipSetDevice(dev->ordinal));
+  const kpe::DeviceCorpus& D = *c->d;
+  if (D.ordinal != dev->ordinal) return fail(KPE_E_STATE, "corpus not uploaded to this device");
+  hipStream_t s = D.bind.last ? D.bind.last : dev->stream;  // behind a pending keep
+  HIPCHK(hipMemcpyAsync(out, D.kept.as<uint8_t>() + (size_t)row0 * R, (size_t)nrows * R, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return KPE_OK;
 }

@@ -84,6 +84,16 @@ hipError_t kpe_launch_gather_rows(const uint8_t* v, uint32_t R, const uint64_t* 
 hipError_t kpe_launch_delta_transitions(const uint8_t* vnew, const uint8_t* vold, uint64_t n, uint32_t Rn, uint32_t Ro,
                                         const uint32_t* tab, unsigned long long* out, hipStream_t s);
 uint32_t kpe_delta_max_rules(void);
+// policy edits on a kept result (kpe_results_splice): out (n x rn) from kept (n x Ro) and sub (n x Rs).
+// col: 2 rn words, per output column {source column | 0x80000000 for a column of sub, partner kept
+// column in bits 0-15 (0xFFFF: none) | `always` mask in bits 16-23} (the second word counts for
+// columns of sub only); unmapped: Ro bytes, non-zero for a kept column that is neither copied nor a
+// partner (NULL: there is none); flags: n bytes, one per row, each written once. out is 16-byte
+// aligned and overlaps neither input. Ro, Rs, rn <= kpe_delta_max_rules().
+hipError_t kpe_launch_splice(const uint8_t* kept, const uint8_t* sub, uint64_t n, uint32_t Ro, uint32_t Rs, uint32_t rn,
+                             const uint32_t* col, const uint8_t* unmapped, uint8_t* out, uint8_t* flags, hipStream_t s);
+uint32_t kpe_splice_rows_per_group(uint32_t Ro, uint32_t Rs, uint32_t rn);  // rows of a group of that pass
+uint32_t kpe_splice_grid(void);                                             // its most blocks
 // result deltas across corpora (kpe_changed_pairs). pairs: npairs x {row of vnew, row of vold};
 // tab / unmapped as above; flags: npairs bytes, one per pair, each written once.
 hipError_t kpe_launch_delta_pairs(const uint8_t* vnew, const uint8_t* vold, const uint64_t* pairs, uint64_t npairs,

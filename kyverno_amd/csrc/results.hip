@@ -9,6 +9,7 @@
 //  kpe_select_*_kernel, kpe_row_summary_kernel — sparse result fetch.
 //  kpe_ns_count*_kernel  — per-namespace rule counts.
 //  kpe_delta_*_kernel, kpe_gather_rows_kernel — result deltas against a kept matrix.
+//  kpe_splice_kernel     — a policy edit's columns spliced into the kept matrix (kpe_results_splice).
 //  kpe_row_fp_kernel, kpe_fp_diff_kernel, kpe_fp_gather_kernel — row fingerprints and their compare.
 //  kpe_report_need_count_kernel, kpe_report_need_scatter_kernel, kpe_fe_words_gather_kernel — the
 //                          report detail of a row list (check mask words, condition trace words,
@@ -627,6 +628,83 @@ extern "C" hipError_t kpe_launch_delta_transitions(const uint8_t* vnew, const ui
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------
+// Policy edits on a kept result (kpe_results_splice): the new kept matrix K' from the kept one K and
+// the evaluation E of the edited policies alone, column by column through a plan, and one flag
+// byte per row by the rule of the flag pass above restricted to E's columns and the kept columns
+// that vanish (splice.inl, shared with scripts/splice_check.cpp). One pass, N x (Ro + Rs + rn + 1)
+// algorithmic bytes; the row list is the selection chain over the flag bytes (kpe_spliced_rows). No
+// global atomics and no zeroing pass: a row's cells and its flag byte are written once, by the
+// block that owns the row's group.
+#define KPE_SPLICE_FN __host__ __device__ __forceinline__
+#define KPE_SPLICE_DEV __device__ __forceinline__
+namespace {
+__device__ __forceinline__ void splice_load16(const uint8_t* __restrict__ p, uint32_t cnt, uint32_t* w) {
+  const Cells16 c = load_cells(p, 0, cnt);
+  w[0] = c.w[0], w[1] = c.w[1], w[2] = c.w[2], w[3] = c.w[3];
+}
+__device__ __forceinline__ void splice_store16(uint8_t* p, const uint32_t* w) {
+  *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ void splice_lds_store16(uint8_t* p, const uint32_t* w) {
+  *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ void splice_lds_load16(const uint8_t* p, uint32_t* w) {
+  const uint4 q = *reinterpret_cast<const uint4*>(p);
+  w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+}
+#include "splice.inl"
+}  // namespace
+constexpr uint32_t kSpliceGrid = 2048;  // persistent blocks (8 per CU)
+
+// All LDS is dynamic, so its base is 16-byte aligned for the staging stores (splice_lds).
+__global__ void __launch_bounds__(256) kpe_splice_kernel(const uint8_t* __restrict__ kept, const uint8_t* __restrict__ sub,
+                                                         uint64_t n, uint32_t Ro, uint32_t Rs, uint32_t rn, uint32_t rpg,
+                                                         const uint32_t* __restrict__ col,
+                                                         const uint8_t* __restrict__ unmapped, uint8_t* __restrict__ out,
+                                                         uint8_t* __restrict__ flags) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_splice[];
+  const uint32_t t = threadIdx.x;
+  const SpliceLds L = splice_lds(Ro, Rs, rn, rpg);
+  uint8_t* s_k = s_splice;
+  uint8_t* s_e = s_splice + L.e_off;
+  uint8_t* s_o = s_splice + L.o_off;
+  uint32_t* s_flag = reinterpret_cast<uint32_t*>(s_splice + L.flag_off);
+  uint32_t* s_col = reinterpret_cast<uint32_t*>(s_splice + L.col_off);
+  uint8_t* s_unm = s_splice + L.unm_off;
+  for (uint32_t i = t; i < 2u * rn; i += 256u) s_col[i] = col[i];
+  if (unmapped)
+    for (uint32_t i = t; i < Ro; i += 256u) s_unm[i] = unmapped[i];
+  const uint64_t ngroups = (n + rpg - 1u) / rpg;
+  for (uint64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const SpliceGroup G = splice_group(g, n, Ro, Rs, rn, rpg);
+    splice_stage(G, t, kept, sub, s_k, s_e, s_flag);
+    __syncthreads();  // the first one also covers the tables
+    splice_build(G, t, Ro, Rs, rn, s_col, s_k, s_e, s_o, s_flag);
+    if (unmapped) splice_sweep(G, t, Ro, s_unm, s_k, s_flag);  // uniform
+    __syncthreads();
+    splice_write(G, t, s_o, s_flag, out, flags);
+    __syncthreads();
+  }
+}
+
+extern "C" uint32_t kpe_splice_rows_per_group(uint32_t Ro, uint32_t Rs, uint32_t rn) {
+  return splice_rows_per_group(Ro, Rs, rn);
+}
+extern "C" uint32_t kpe_splice_grid(void) { return kSpliceGrid; }
+extern "C" hipError_t kpe_launch_splice(const uint8_t* kept, const uint8_t* sub, uint64_t n, uint32_t Ro, uint32_t Rs,
+                                        uint32_t rn, const uint32_t* col, const uint8_t* unmapped, uint8_t* out,
+                                        uint8_t* flags, hipStream_t s) {
+  if (!n) return hipSuccess;
+  if (Ro > kSpliceMaxRules || Rs > kSpliceMaxRules || rn > kSpliceMaxRules) return hipErrorInvalidValue;
+  const uint32_t rpg = splice_rows_per_group(Ro, Rs, rn);
+  const uint64_t ngroups = (n + rpg - 1u) / rpg;
+  const dim3 grid((unsigned)std::min<uint64_t>(ngroups, kSpliceGrid));
+  hipLaunchKernelGGL(kpe_splice_kernel, grid, dim3(256), (size_t)splice_lds(Ro, Rs, rn, rpg).total, s, kept, sub, n, Ro, Rs,
+                     rn, rpg, col, unmapped, out, flags);
+  return hipGetLastError();
 }
 
 // Result deltas across corpora (kpe_changed_pairs): pair k = {new_row, old_row}, row new_row of the

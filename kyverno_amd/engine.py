@@ -508,6 +508,76 @@ class Engine:
         k = min(total, n)
         return rows[:k], (vr[:k] if with_verdicts else np.zeros((0, R), dtype=np.uint8)), total
 
+    # ---- policy edits on a kept result (evaluate the edited policies alone, splice their columns in) ----
+    @staticmethod
+    def _names_arg(names):
+        b = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        return (ctypes.c_char_p * max(len(b), 1))(*b), len(b)
+
+    def splice_plan(self, sub: PolicySet, corpus: Corpus, removed=()) -> np.ndarray:
+        """The column plan kpe_results_splice would follow (kpe_splice_plan; host only): per column
+        of the new kept matrix the kept column it copies, or -1 - s for column s of sub."""
+        arr, k = self._names_arg(removed)
+        L = load()
+        rn = L.kpe_splice_plan(corpus.h, sub.h, arr, k, None, 0)
+        if rn < 0:
+            check(-rn)
+        plan = np.zeros(max(rn, 1), dtype=np.int32)
+        rn = L.kpe_splice_plan(corpus.h, sub.h, arr, k, plan.ctypes.data, rn)
+        if rn < 0:
+            check(-rn)
+        return plan[:rn]
+
+    def splice_results(self, sub: PolicySet, corpus: Corpus, removed=(), always=0) -> int:
+        """After an evaluation of `sub` (the edited and added policies compiled alone) on a corpus
+        with a kept result: splice its columns into the kept matrix, drop the columns of the
+        `removed` policies (kpe_results_splice) and return the number of changed rows; the kept
+        result and kept_rule_names are then the new PolicySet's. always: a mask of kpe_verdict
+        bits (SEL(v)) per rule of sub, or one for all. Costs a second matrix buffer on the device."""
+        R = sub.num_rules
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(always, dtype=np.uint8), (R,)) if np.ndim(always) == 0
+                                 else np.asarray(always, dtype=np.uint8))
+        if a.shape != (R,):
+            raise ValueError("always: one mask, or one per rule of sub")
+        abuf = a if R else np.zeros(1, dtype=np.uint8)
+        arr, k = self._names_arg(removed)
+        t = load().kpe_results_splice(self.device.h, sub.h, corpus.h, arr, k, abuf.ctypes.data)
+        if t < 0:
+            check(-t)
+        return int(t)
+
+    def spliced_rows(self, corpus: Corpus, with_verdicts=True, cap: Optional[int] = None):
+        """The changed rows of the last splice_results on corpus (kpe_spliced_rows): (rows uint64
+        ascending, their rows of the new kept matrix (k, R) uint8, total). cap: at most that many
+        rows come back; None: a count call, then one of that size. Nothing is compared again."""
+        L = load()
+        R = max(L.kpe_results_kept_rules(corpus.h), 0)
+
+        def call(rows, vr, n):
+            t = L.kpe_spliced_rows(self.device.h, corpus.h, rows.ctypes.data if n else None,
+                                   vr.ctypes.data if (vr is not None and n and R) else None, n)
+            if t < 0:
+                check(-t)
+            return int(t)
+
+        n = call(None, None, 0) if cap is None else min(int(cap), corpus.n)
+        rows = np.zeros(n, dtype=np.uint64)
+        vr = np.zeros((n, R), dtype=np.uint8) if with_verdicts else None
+        total = call(rows, vr, n) if (n or cap is not None) else 0
+        k = min(total, n)
+        return rows[:k], (vr[:k] if with_verdicts else np.zeros((0, R), dtype=np.uint8)), total
+
+    def kept_results(self, corpus: Corpus) -> Optional[np.ndarray]:
+        """The kept matrix (N x kept R uint8), read back whole (kpe_results_kept_fetch): diagnostics
+        and tests. None when nothing is kept."""
+        L = load()
+        R = L.kpe_results_kept_rules(corpus.h)
+        if R < 0:
+            return None
+        out = np.zeros((corpus.n, R), dtype=np.uint8)
+        check(L.kpe_results_kept_fetch(self.device.h, corpus.h, 0, corpus.n, out.ctypes.data if out.size else None))
+        return out
+
     def delta_transitions(self, ps: PolicySet, corpus: Corpus, column_map=None) -> np.ndarray:
         """Per rule of ps the 8 x 8 table [kept code, new code] of the corpus's rows
         (kpe_delta_transitions): (R, 8, 8) uint64; the kept code is KPE_NA for an unmapped rule."""
@@ -1060,6 +1130,72 @@ def delta_transitions(old, new, column_map) -> np.ndarray:
     check(load().kpe_delta_transitions_host(o.ctypes.data if o.size else None, v.ctypes.data if v.size else None, n,
                                             Ro, Rn, m.ctypes.data, out.ctypes.data if Rn else None))
     return out
+
+
+def splice_plan(kept_names: Sequence[str], sub_names: Sequence[str], removed: Sequence[str] = ()):
+    """The plan of kpe_results_splice from two lists of "<policy>/<rule>" names and the removed
+    policies' names, written out in Python: (plan, partner), both int32. plan[r] is the kept column
+    that column r of the new kept matrix copies, or -1 - s for column s of sub; partner[s] is the
+    kept column named like column s of sub, or -1. An edited policy's columns stand where its first
+    kept column stood, in sub's order; added policies are appended. KPE_E_INVALID for a name that
+    occurs twice on either side or a removed policy sub also holds, as there."""
+    kept = {}
+    for i, nm in enumerate(kept_names):
+        if nm in kept:
+            raise KpeError(1, f"kept rule name occurs twice: {nm}")
+        kept[nm] = i
+    if len(set(sub_names)) != len(sub_names):
+        raise KpeError(1, "rule name occurs twice")
+    pol = lambda nm: nm.split("/", 1)[0]
+    by_policy = {}  # in sub's order (dicts keep insertion order)
+    for s, nm in enumerate(sub_names):
+        by_policy.setdefault(pol(nm), []).append(s)
+    gone = set(removed)
+    if gone & set(by_policy):
+        raise KpeError(1, "removed policy is also edited")
+    plan, emitted = [], set()
+    for c, nm in enumerate(kept_names):
+        p = pol(nm)
+        if p in by_policy:
+            if p not in emitted:
+                emitted.add(p)
+                plan += [-1 - s for s in by_policy[p]]
+        elif p not in gone:
+            plan.append(c)
+    for p, cols in by_policy.items():
+        if p not in emitted:
+            plan += [-1 - s for s in cols]
+    return np.array(plan, dtype=np.int32), np.array([kept.get(nm, -1) for nm in sub_names], dtype=np.int32)
+
+
+def splice_names(kept_names: Sequence[str], sub_names: Sequence[str], plan) -> List[str]:
+    """The rule names of the spliced matrix: kept names for copied columns, sub's for the others."""
+    return [kept_names[int(e)] if e >= 0 else sub_names[-1 - int(e)] for e in plan]
+
+
+def splice_results(kept, sub, plan, partner, always=0):
+    """kpe_results_splice over matrices the caller holds (kpe_results_splice_host; no device call):
+    kept (n, Ro), sub (n, Rs), plan and partner as splice_plan gives them, always a mask of
+    kpe_verdict bits (SEL(v)) per column of sub or one for all. Returns (the new kept matrix (n, rn)
+    uint8, the row flags (n,) uint8 of 0 / 1, the number of changed rows)."""
+    k, e = _delta_matrices(kept, sub)
+    n, Ro, Rs = k.shape[0], k.shape[1], e.shape[1]
+    pl = np.ascontiguousarray(plan, dtype=np.int32)
+    rn = pl.shape[0]
+    pa, a = _delta_args(Rs, partner, always)
+    out = np.zeros((n, rn), dtype=np.uint8)
+    flags = np.zeros(max(n, 1), dtype=np.uint8)
+    t = load().kpe_results_splice_host(k.ctypes.data if k.size else None, e.ctypes.data if e.size else None, n, Ro, Rs, rn,
+                                       pl.ctypes.data if rn else None, pa.ctypes.data, a.ctypes.data,
+                                       out.ctypes.data if out.size else None, flags.ctypes.data)
+    if t < 0:
+        check(-t)
+    return out, flags[:n], int(t)
+
+
+def splice_bytes(n: int, Ro: int, Rs: int, rn: int) -> float:
+    """The algorithmic bytes of the splice pass: n x (Ro + Rs + rn + 1) (kpe_splice_bytes)."""
+    return float(load().kpe_splice_bytes(n, Ro, Rs, rn))
 
 
 FP_MASKS = 1  # include/kpe.h KPE_FP_MASKS: FAIL cells' check mask words count

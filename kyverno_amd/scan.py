@@ -316,7 +316,11 @@ class ResidentScanner:
     Namespace label changes (controller.go:310-318 reads the labels fresh at every rescan) are
     applied in place too: `set_namespace_labels` replaces the label table of every segment on the
     device and returns the rows whose report changes; with ns_objects=True `update` reads them off
-    the Namespace objects among its events."""
+    the Namespace objects among its events.
+
+    One policy edited, added or removed out of many (controller.go:379-419 keeps the stored results
+    of unchanged policies): `apply_edit` evaluates the edited policies alone and splices their
+    columns into the kept matrix (Engine.splice_results), keep="matrix" only."""
 
     MESSAGE_CODES = SEL(2) | SEL(4) | SEL(5)  # FAIL, ERROR, SKIP: results whose message the policy text decides
 
@@ -368,11 +372,29 @@ class ResidentScanner:
                 raise KpeError(2, "keyed: one NDJSON line per corpus row")  # KPE_E_INVALID
             self._map = RowMap([_key(r, i) for i, r in enumerate(self._lines)],
                                resource_hashes(b"\n".join(self._lines)), max_segments, max_retired)
-        self._applied = None  # the PolicySet of the last apply (what `reports` renders)
+        self._applied_v = None  # the PolicySet of the last apply (what `reports` renders), or after an
+        # apply_edit a callable that makes it (see the _applied property)
+        self._edit = None  # the partial PolicySet of an apply_edit, while the segments' last evaluation is of it
+        self._edit_ok = False  # reports(policies="edited") may render from it: nothing happened since
         self.edits = dict(edits or {})  # policy name -> edits seen (keep="fingerprints": folded into msg_salts)
         if fingerprints is not None:
             engine.load_fingerprints(self.corpus, fingerprints)
         self.last_stats = {}
+
+    @property
+    def _applied(self):
+        """The PolicySet of the last apply. After apply_edit(full, ...) with a callable `full` it
+        is made (compiled) here, by the first reader that needs the whole set."""
+        a = self._applied_v
+        if a is not None and callable(a):
+            a = self._applied_v = a()
+            if self._policies is not None:
+                self._policies = a
+        return a
+
+    @_applied.setter
+    def _applied(self, ps):
+        self._applied_v = ps
 
     @property
     def resource_hashes(self):
@@ -438,6 +460,7 @@ class ResidentScanner:
                 [self.MESSAGE_CODES if n.split("/", 1)[0] in names else 0 for n in policies.rule_names], dtype=np.uint8), None)
         eng.evaluate_async(policies, corpus, masks=self._with_reports)
         self._applied = policies
+        self._stale, self._edit = False, None
         if self._policies is None:
             v, _, _ = eng.fetch(policies, corpus)  # nothing to compare with: the whole matrix, once
             out = {int(i): v[i].copy() for i in np.flatnonzero((v != 0).any(axis=1))}
@@ -480,6 +503,7 @@ class ResidentScanner:
             elif ps is not None:
                 stats["rows"] = self.corpus.n
                 eng.evaluate_async(ps, self.corpus, masks=self._with_reports)
+                self._stale, self._edit = False, None
                 if self.keep == "fingerprints":
                     rows, vr, _, _ = eng.changed_rows_fp(ps, self.corpus, msg_salts=self._msg, msg_codes=self.MESSAGE_CODES)
                 else:
@@ -493,11 +517,11 @@ class ResidentScanner:
     def _refresh(self):
         """Evaluate the segments again when rows were retired since their last evaluation: a
         retired row gives no response from the next evaluation on."""
-        if self._applied is None:
+        if self._applied_v is None:
             raise KpeError(5, "no apply yet")  # KPE_E_STATE
         if self._stale:
             self.engine.evaluate_batch_async(self._applied, self._segs, masks=self._with_reports)
-            self._stale = False
+            self._stale, self._edit = False, None
 
     def namespace_counts(self):
         """Per-namespace rule counts of the resident corpus under the last applied PolicySet:
@@ -524,23 +548,90 @@ class ResidentScanner:
                 out[k] += t[k]
         return out
 
-    def reports(self, rows):
+    def reports(self, rows, policies=None):
         """{row: PolicyReport results} of the listed rows under the last applied PolicySet, with
         messages (Engine.report_rows: one sparse fetch of what the rows' entries need, one bulk
-        render). Needs reports=True; typically called with the rows `apply` returned."""
+        render). Needs reports=True; typically called with the rows `apply` returned.
+
+        policies="edited", right after an `apply_edit`: only the entries of the edited and added
+        policies, rendered from the partial evaluation; what a consumer swaps into the stored
+        report, as the background controller does (controller.go:379-419). KPE_E_STATE once
+        anything else happened. The default evaluates the full set first when the last evaluation
+        was a partial one."""
         if not self._with_reports:
             raise KpeError(5, "ResidentScanner(reports=True) keeps what reports() needs")  # KPE_E_STATE
-        if self._applied is None:
+        if self._applied_v is None:
             raise KpeError(5, "no apply yet")
+        if policies not in (None, "edited"):
+            raise ValueError('policies: None or "edited"')
+        if policies == "edited":
+            if self._edit is None or not self._edit_ok:
+                raise KpeError(5, 'reports(policies="edited"): only right after an apply_edit')
+            ps = self._edit
+        else:
+            if self._edit is not None:  # the segments' last evaluation is of the edited policies alone
+                self._refresh()
+            ps = self._applied
         rows = [int(i) for i in rows]
+        if not ps.num_rules:
+            return {i: [] for i in rows}
         if not self._keyed:
-            res = self.engine.report_rows(self._applied, self.corpus, rows, resources=[self._lines[i] for i in rows])
+            res = self.engine.report_rows(ps, self.corpus, rows, resources=[self._lines[i] for i in rows])
             return dict(zip(rows, res))
         out = {i: [] for i in rows}  # a deleted resource has no report
         for s, pr in self._map.group(rows).items():
-            res = self.engine.report_rows(self._applied, self._segs[s], [r for _, r in pr],
+            res = self.engine.report_rows(ps, self._segs[s], [r for _, r in pr],
                                           resources=[self._lines[l] for l, _ in pr])
             out.update(zip((l for l, _ in pr), res))
+        return out
+
+    # ---- policy edits: evaluate the edited policies alone ----
+    def apply_edit(self, full, edited, removed=()):
+        """`apply` for the usual event, one policy edited, added or removed out of hundreds: only
+        `edited`, a PolicySet of the edited and added policies alone (with the exceptions naming
+        them), is evaluated, its columns are spliced into the kept matrix on the device and the
+        columns of the `removed` policies (names) are dropped (Engine.splice_results). The
+        background controller likewise keeps the stored results of unchanged policies and
+        recomputes only the changed ones (controller.go:379-419); a rule's verdict depends on no
+        other policy. Returns {row: verdict row under the new set}, the rows `apply(full,
+        edited=names of edited)` would return: FAIL / ERROR / SKIP cells of `edited` always count.
+
+        full: the complete new PolicySet, or a zero-argument callable returning it, called only when
+        something needs the whole set (namespace_counts, cli_summary, reports, matrix, update,
+        set_namespace_labels, compact, which evaluate it first). Rules are paired by name, so the
+        rules of `edited` must carry the names they have in `full`.
+
+        keep="matrix" only: keep="fingerprints" raises ValueError, since a fingerprint cannot give
+        back the old cells of the edited policy to take them out. KPE_E_STATE before the first
+        `apply`. Check masks and traces of the unchanged policies are not kept: reports render them
+        from a full evaluation, reports(rows, policies="edited") renders the edited policies'
+        entries from this one. Costs a second matrix buffer per segment on the device."""
+        if self.keep == "fingerprints":
+            raise ValueError('apply_edit: keep="matrix" only (a fingerprint cannot give back the old cells)')
+        if self._applied_v is None or self._policies is None:
+            raise KpeError(5, "no apply yet")  # KPE_E_STATE
+        eng = self.engine
+        removed = list(removed)
+        if edited.num_rules:  # nothing to evaluate when policies are only removed
+            eng.evaluate_batch_async(edited, self._segs, masks=self._with_reports)
+        self._edit, self._edit_ok = edited, True
+        self._stale = True  # the segments' last evaluation is not of the applied set: _refresh evaluates it
+        always = np.full(edited.num_rules, self.MESSAGE_CODES, dtype=np.uint8)
+        out = {}
+        for s, seg in enumerate(self._segs):
+            total = eng.splice_results(edited, seg, removed, always)
+            if not total:
+                continue
+            rows, vr, _ = eng.spliced_rows(seg, cap=total)
+            if self._keyed:
+                for k, l in self._map.translate(s, rows):
+                    out[l] = vr[k].copy()
+            else:
+                out.update((int(i), vr[k].copy()) for k, i in enumerate(rows))
+        self._applied = full
+        self._policies = full
+        self.last_stats = {"rows": self._map.n_live if self._keyed else self.corpus.n, "changed": len(out),
+                           "segments": len(self._segs), "partial": True, "columns": edited.num_rules}
         return out
 
     # ---- resource churn (keyed=True) ----
@@ -555,7 +646,7 @@ class ResidentScanner:
         eng, m = self.engine, self._map
         eng.evaluate_batch_async(policies, self._segs, masks=self._with_reports)
         self._applied = policies
-        self._stale = False
+        self._stale, self._edit = False, None
         out = {}
         for s, seg in enumerate(self._segs):
             if msg is not None:
@@ -613,6 +704,7 @@ class ResidentScanner:
             if events:  # before the delta segment is flattened: it takes the new table
                 relabel = self.set_namespace_labels(events)
                 relabelled = self.last_stats["relabelled"]
+        self._edit_ok = False  # the segments change: the partial evaluation's entries are no longer offered
         offered =list(zip((_key(r, i) for i, r in enumerate(lines)), resource_hashes(b"\n".join(lines)))) if lines else []
         plan = m.plan(offered, deletes)
         items = plan["items"]
@@ -688,7 +780,7 @@ class ResidentScanner:
             raise KpeError(2, "compact: one corpus row per live resource")  # KPE_E_INVALID
         self._segs = [seg]
         self.corpus = seg
-        self._stale = False
+        self._stale, self._edit = False, None
         if self._applied is not None:
             eng.evaluate_async(self._applied, seg, masks=self._with_reports)
             if self.keep != "fingerprints":
@@ -702,8 +794,10 @@ class ResidentScanner:
         resource's row is all NA): (logical rows, R) uint8. Diagnostics and tests: it fetches every
         segment's matrix."""
         self._need_keyed()
-        if self._applied is None:
+        if self._applied_v is None:
             raise KpeError(5, "no apply yet")
+        if self._edit is not None:  # the segments' last evaluation is of the edited policies alone
+            self._refresh()
         out = np.zeros((self._map.n_logical, self._applied.num_rules), dtype=np.uint8)
         for s, seg in enumerate(self._segs):
             v, _, _ = self.engine.fetch(self._applied, seg)
