@@ -151,7 +151,8 @@ struct kpe_device {
   // verdict-only form reads the wide records, not the corpus's compact columns; bit 5, i.e. 32:
   // the compact form gathers each pod's items from rec12 / cw4, not the scatter form over the
   // owner-tagged columns; bit 6, i.e. 64: scatter launches of two or four tiles per wave read
-  // rec12 as those of one tile do, not the pod word column pw4)
+  // rec12 as those of one tile do, not the pod word column pw4; bit 7, i.e. 128: narrow launches
+  // of four tiles per wave keep the per-tile form, not the group form)
   bool no_cache = false, patvm_err = false;
   // the general scan of a podSecurity program walks each pod's lists itself; KPE_PSUM=1: it reads
   // per-pod records kpe_psum_kernel builds right before it on the second stream (round 6: C4 step
@@ -162,6 +163,7 @@ struct kpe_device {
   uint32_t lean_tpw = 0, lean_shape = 0;
   int lean_form = -1;  // what the last kpe_lean6_kernel launch read (kpe_debug_lean_form)
   int lean_narrow = 0;  // and whether it was the narrow scatter form (kpe_debug_lean_narrow)
+  int lean_group = 0;   // and whether that was its group form (kpe_debug_lean_group)
   // kpe_lean6_kernel's pod-evidence table (kernels_abi.h kpe_l6_pod_table_word), built at
   // kpe_device_open: it depends on neither the policies nor a corpus
   kpe::DevBuf lean_pod_tab;

@@ -603,23 +603,37 @@ struct LeanPackArgs {
 // what the scatter form of the compact verdict-only evaluation reads instead of cw4 and the
 // volume, sysctl and annotation columns. Every list item carries its owner, the index of its pod
 // in the pod's 64-pod tile (row & 63), in bits 26-31 of its first word, so the lane that loaded an
-// item can OR the item's evidence into its pod's word without knowing the pod's offsets. The
-// owner is layout (CSR to COO): no code, no evidence, nothing of a policy. A list slot is an item
-// of the tile when its index is below the tile's item count; there is no "real" bit.
-//   container word   states 0-14 and capability-set id 15-25 as in cw4, owner 26-31
-//   sysctl word      id | owner << 26
-//   annotation pair  {key id | owner << 26, value id}
-//   volume word      the source as KPE_L6T_VOL_*, owner 26-31
-// Ids are masked to 26 bits: KPE_NO_STR stays past every dictionary below 2^26 - 1 entries, and a
+// item can OR the item's evidence into its pod's word without knowing the pod's offsets. Volume,
+// sysctl and annotation items also carry their quarter, the pod's tile within its group of four
+// consecutive tiles (tile & 3), in bits 24-25: byte 3 of the word is then 4 * owner + quarter,
+// the pod's index in the 256 interleaved words of a wave that evaluates the four tiles as one
+// group (lean.inl l6_group_tiles). The per-tile forms read the owner alone. Owner and quarter are
+// layout (CSR to COO): no code, no evidence, nothing of a policy. A list slot is an item of the
+// tile (of the group) when its index is below the tile's (the group's) item count; there is no
+// "real" bit.
+//   container word   states 0-14 and capability-set id 15-25 as in cw4, owner 26-31 (no quarter:
+//                    the word is full)
+//   sysctl word      id | quarter << 24 | owner << 26
+//   annotation pair  {key id | quarter << 24 | owner << 26, value id}
+//   volume word      the source as KPE_L6T_VOL_*, quarter 24-25, owner 26-31
+// Ids are masked to 24 bits: KPE_NO_STR stays past every dictionary below 2^24 - 1 entries, and a
 // corpus with a larger sysctl or annotation-key dictionary keeps cw4 and the gather form.
 #define KPE_L6T_OWNER_SH 26
-#define KPE_L6T_ID_MASK ((1u << KPE_L6T_OWNER_SH) - 1u)
+#define KPE_L6T_QUARTER_SH 24
+#define KPE_L6T_ID_MASK ((1u << KPE_L6T_QUARTER_SH) - 1u)
 static_assert((KPE_L6C_ID_MASK << KPE_L6C_ID_SH) < (1u << KPE_L6T_OWNER_SH), "the owner overlaps the capability-set id");
 KPE_L6_FN uint32_t kpe_l6_tag_owner(uint32_t w) { return w >> KPE_L6T_OWNER_SH; }
+KPE_L6_FN uint32_t kpe_l6_tag_quarter(uint32_t w) { return (w >> KPE_L6T_QUARTER_SH) & 3u; }
+// 4 * owner + quarter: byte 3 of a volume, sysctl or annotation-key word
+KPE_L6_FN uint32_t kpe_l6_tag_slot(uint32_t w) { return w >> KPE_L6T_QUARTER_SH; }
 KPE_L6_FN uint32_t kpe_l6_tag_ctr(uint32_t cx, uint32_t cy, uint32_t owner) {
   return kpe_l6_pack_cx(cx) | ((CY_CAPSET(cy) & KPE_L6C_ID_MASK) << KPE_L6C_ID_SH) | (owner << KPE_L6T_OWNER_SH);
 }
+// (the builders without a quarter give quarter 0)
 KPE_L6_FN uint32_t kpe_l6_tag_id(uint32_t id, uint32_t owner) { return (id & KPE_L6T_ID_MASK) | (owner << KPE_L6T_OWNER_SH); }
+KPE_L6_FN uint32_t kpe_l6_tagq_id(uint32_t id, uint32_t owner, uint32_t quarter) {
+  return kpe_l6_tag_id(id, owner) | (quarter << KPE_L6T_QUARTER_SH);
+}
 KPE_L6_FN uint32_t kpe_l6_tag_get_id(uint32_t w) { return w & KPE_L6T_ID_MASK; }
 // A volume's source mask (VS_* bits, 29 of them) as an index: a volume with exactly one source
 // holds the source's VS_* number, one with none the number 31 (no source has it), and the
@@ -633,6 +647,9 @@ KPE_L6_FN uint32_t kpe_l6_tag_vol(uint32_t src, uint32_t owner) {
   const uint32_t w = src == 0u ? KPE_L6T_VOL_IDX : (src & (src - 1u)) == 0u ? (uint32_t)__builtin_ctz(src) : KPE_L6T_VOL_ESC;
   return w | (owner << KPE_L6T_OWNER_SH);
 }
+KPE_L6_FN uint32_t kpe_l6_tagq_vol(uint32_t src, uint32_t owner, uint32_t quarter) {
+  return kpe_l6_tag_vol(src, owner) | (quarter << KPE_L6T_QUARTER_SH);
+}
 // vol_code (bit 0 hostPath, bit 1 outside the restricted set) of a volume word without KPE_L6T_VOL_ESC
 KPE_L6_FN uint32_t kpe_l6_vol_decide(uint32_t w) {
   const uint32_t i = w & KPE_L6T_VOL_IDX;
@@ -640,8 +657,17 @@ KPE_L6_FN uint32_t kpe_l6_vol_decide(uint32_t w) {
 }
 // The four tagged columns in one device allocation (LeanShard::cw4 is its base in a scatter
 // launch): containers at 0, then volumes, sysctls and annotation pairs at 256-byte boundaries,
-// then KPE_L6T_SLACK bytes that the clamped over-reads of the last tile end in.
-#define KPE_L6T_SLACK 1024u
+// then KPE_L6T_SLACK bytes that the over-reads of the last tile or group end in (the group form
+// loads KPE_L6G_VOL_SETS sets of 64 volume words from a group's first volume on: 1,536 bytes).
+#define KPE_L6T_SLACK 2048u
+// The group form's 64-slot sets loaded up front per 256-pod group (the rest: a wave-uniform loop).
+// A group of the C2 corpus (synth.cpp) averages 344 volumes, 12 sysctls and 77 annotations.
+#define KPE_L6G_VOL_SETS 6
+#define KPE_L6G_SYS_SETS 1
+#define KPE_L6G_ANN_SETS 2
+static_assert(KPE_L6G_VOL_SETS * 256u <= KPE_L6T_SLACK && KPE_L6G_ANN_SETS * 512u <= KPE_L6T_SLACK, "slack");
+// Per-wave LDS of the group form: 256 evidence words (word 4 * pod + quarter), then the rows.
+#define KPE_L6G_ACC_BYTES 1024u
 struct KpeL6TagLayout {
   uint64_t o_vol, o_sys, o_ann, bytes;  // byte offsets; bytes: the allocation with its slack
 };

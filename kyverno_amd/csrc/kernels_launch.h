@@ -30,7 +30,8 @@ hipError_t kpe_launch_scan(const ScanArgs* dargs, int64_t n, int pss, int kind, 
 hipError_t kpe_launch_prep(const ScanArgs* dargs, int pss, int narrow, size_t dyn_bytes, hipStream_t s);
 hipError_t kpe_launch_selmask(const SelMaskArgs* a, hipStream_t s);
 // cp: 0 the wide records, 1 the compact columns (gather form), 2 the owner-tagged columns (scatter form),
-// 3 the same with the pod word column in LeanShard::rec12 (narrow form; tpw 2 or 4)
+// 3 the same with the pod word column in LeanShard::rec12 (narrow form; tpw 2 or 4), 4 the narrow form's
+// group form (tpw 4; LeanBatchArgs::wave_words sized for it)
 hipError_t kpe_launch_lean6(const LeanBatchArgs* a, size_t dyn_bytes, int lc, int sann, int cv, int cp, hipStream_t s);
 int kpe_lean6_compact(int lc, int cv);  // may a launch of that shape read the compact columns (cp)?
 hipError_t kpe_launch_lean_pack(const LeanPackArgs* a, hipStream_t s);

@@ -432,7 +432,7 @@ kpe_status run_codes(const kpe::Corpus& C, kpe::DeviceCorpus& D, hipStream_t s) 
 // corpus bound to kpe_lean6_kernel. rec12 always (kpe_lean_pack_kernel); then what the device's
 // selected shape reads: the owner-tagged columns of the scatter form (kpe_lean_tag_kernel: one
 // zeroed allocation, kernels_abi.h kpe_l6_tag_layout), or cw4 when `gather` asks for the gather
-// form or the tagged columns cannot hold the corpus (an id dictionary past their 26 bits, or more
+// form or the tagged columns cannot hold the corpus (an id dictionary past their 24 bits, or more
 // than 4 GiB of them: the kernel's byte offsets are 32 bits). rec12 and cw4 carry 128 bytes of
 // slack; the kernel's descriptors end at n * 12 and nctr * 4 bytes (loads past those return 0).
 kpe_status run_lean_pack(const kpe::Corpus& C, kpe::DeviceCorpus& D, hipStream_t s, bool gather) {
@@ -1455,6 +1455,9 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
   }
   cp = sc || ga;
   nw = nw && sc;
+  // gr: the group form of the narrow form at four tiles per wave (the tagged columns always hold
+  // the quarters it indexes with; KPE_LEAN6_SHAPE bit 7: the per-tile form everywhere)
+  const bool gr = nw && tpw == 4 && !(dev->lean_shape & 128u);
   uint32_t acc = 0, kt_max = 0;
   *bytes = 0;
   for (size_t k = 0; k < m; ++k) {
@@ -1483,7 +1486,10 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
   a.blk0[m] = acc;
   a.kt_words = (kt_max + 3u) & ~3u;
   a.code_words = lc ? ((code_max + 15u) / 16u) * 4u : 0u;
-  a.wave_words = ((KPE_L6_STAGE_BYTES + std::max(64u * R, 256u) + 15u) / 16u) * 4u;  // rows: a word per pod at least
+  // rows: a word per pod at least (group form: 256 evidence words ahead of them, 1,280 bytes per
+  // wave at R <= 4; with the 1,600 bytes of the pod table a C2 block stays far below the 20 KiB
+  // that eight blocks per CU leave each)
+  a.wave_words = (((gr ? KPE_L6G_ACC_BYTES : KPE_L6_STAGE_BYTES) + std::max(64u * R, 256u) + 15u) / 16u) * 4u;
   if (!cv)
     for (uint32_t c = 0; c < PD.ncls; ++c) {
       const KpeL6ClassMasks m = kpe_l6_class_masks(PD.cls_h[2 * c] & P.cv_union);
@@ -1493,9 +1499,10 @@ kpe_status lean6_launch(kpe_device* dev, const kpe::Program& P, const kpe::Devic
   a.pod_tab = (cp ? dev->lean_pod_tab_c : dev->lean_pod_tab).as<uint32_t>();
   const size_t dyn = 4 * ((size_t)KPE_L6_PT_WORDS + a.kt_words + a.code_words + 4 * (size_t)a.wave_words);
   HIPCHK(kpe_launch_lean6(&a, dyn, lc ? 1 : 0, (a.need & NEED_SANN) || (dev->lean_shape & 1u) ? 1 : 0, cv ? 1 : 0,
-                         nw ? 3 : sc ? 2 : cp ? 1 : 0, s));
+                         gr ? 4 : nw ? 3 : sc ? 2 : cp ? 1 : 0, s));
   dev->lean_form = sc ? 2 : cp ? 1 : 0;
   dev->lean_narrow = nw ? 1 : 0;
+  dev->lean_group = gr ? 1 : 0;
   return KPE_OK;
 }
 
@@ -1595,7 +1602,7 @@ kpe_status kpe_device_open(int ordinal, kpe_device** out) {
     const int t = atoi(ev);
     d->lean_tpw = t == 1 || t == 2 || t == 4 ? (uint32_t)t : 0u;
   }
-  if (const char* ev = getenv("KPE_LEAN6_SHAPE")) d->lean_shape = (uint32_t)atoi(ev) & 0x73u;
+  if (const char* ev = getenv("KPE_LEAN6_SHAPE")) d->lean_shape = (uint32_t)atoi(ev) & 0xF3u;
   for (int k = 0; k < d->nlanes; ++k) {
     e = hipStreamCreateWithFlags(&d->lanes[k], hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -1703,6 +1710,9 @@ int kpe_debug_lean_form(const kpe_device* d) { return d ? d->lean_form : -KPE_E_
 // Diagnostic (not in kpe.h): 1 when that launch was the narrow scatter form, which reads the pod
 // word column pw4, not rec12; else 0.
 int kpe_debug_lean_narrow(const kpe_device* d) { return d ? d->lean_narrow : -KPE_E_INVALID; }
+// Diagnostic (not in kpe.h): 1 when that launch was the group form of the narrow form (a wave's
+// four tiles' volumes, sysctls and annotations streamed as one 256-pod group); else 0.
+int kpe_debug_lean_group(const kpe_device* d) { return d ? d->lean_group : -KPE_E_INVALID; }
 
 kpe_status kpe_corpus_row_flags(const kpe_corpus* c, uint32_t* out) {
   if (!c || !out) return fail(KPE_E_INVALID, "kpe_corpus_row_flags: null argument");

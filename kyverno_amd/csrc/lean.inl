@@ -256,7 +256,8 @@ __global__ void __launch_bounds__(256) kpe_lean_pack_kernel(LeanPackArgs a) {
 // ---- kpe_lean_tag_kernel: the owner-tagged columns of a corpus (once per corpus) ---------------
 // One wave per 64-pod tile, launched where kpe_lean_pack_kernel is: lane i finds pod i's list
 // offsets as kpe_psum_kernel does (tile header plus a wave scan of the packed counts) and writes
-// each of its items with owner i (kernels_abi.h kpe_l6_tag_*). An item outside its column (counts
+// each of its items with owner i and, but for containers, the tile's quarter (kernels_abi.h
+// kpe_l6_tag_*). An item outside its column (counts
 // and headers that disagree) is not written; the allocation is zeroed before the launch.
 __global__ void __launch_bounds__(256) kpe_lean_tag_kernel(LeanTagArgs a) {
   const uint32_t lane = threadIdx.x & 63u;
@@ -279,11 +280,12 @@ __global__ void __launch_bounds__(256) kpe_lean_tag_kernel(LeanTagArgs a) {
     const uint2 e = reinterpret_cast<const uint2*>(a.crec)[k];
     tc[k] = kpe_l6_tag_ctr(e.x, e.y, lane);
   }
-  for (uint32_t k = ov; k < ov + nv && k < a.nvol; ++k) tv[k] = kpe_l6_tag_vol(a.vol[k], lane);
-  for (uint32_t k = os; k < os + ns && k < a.nsys; ++k) ts[k] = kpe_l6_tag_id(a.sys[k], lane);
+  const uint32_t qt = tile & 3u;  // the tile's place in its group of four (the group form's word index)
+  for (uint32_t k = ov; k < ov + nv && k < a.nvol; ++k) tv[k] = kpe_l6_tagq_vol(a.vol[k], lane, qt);
+  for (uint32_t k = os; k < os + ns && k < a.nsys; ++k) ts[k] = kpe_l6_tagq_id(a.sys[k], lane, qt);
   for (uint32_t k = oa; k < oa + na && k < a.npann; ++k) {
     const uint2 q = reinterpret_cast<const uint2*>(a.pann)[k];
-    ta[2u * (size_t)k] = kpe_l6_tag_id(q.x, lane), ta[2u * (size_t)k + 1u] = q.y;
+    ta[2u * (size_t)k] = kpe_l6_tagq_id(q.x, lane, qt), ta[2u * (size_t)k + 1u] = q.y;
   }
 }
 
@@ -914,15 +916,291 @@ __device__ __forceinline__ void l6_scatter_tiles() {
   }
 }
 
+// ---- kpe_lean6_kernel<4, true, SANN, false, true, true, true, true>: the group form of the
+// narrow scatter form at four tiles per wave. A wave's four tiles are one 256-pod group, and the
+// group's volumes, sysctls and annotations are contiguous in their columns: each column is
+// streamed once from the group's first item (hdr[tile0]) to its last (hdr[min(tile0 + 4, ntiles)])
+// in 64-slot sets, KPE_L6G_*_SETS of them loaded in step 2 and the rest in a wave-uniform loop,
+// where the per-tile form loads, codes and ORs two (one) sets per tile however few items the tile
+// has. The item words carry the pod's tile within the group (kernels_abi.h kpe_l6_tag_quarter),
+// so byte 3 of a word is the pod's index in the wave's 256 interleaved evidence words: word
+// 4 * pod + quarter, cleared once per wave. A slot is an item of the group when its index is
+// below the group's count: a slot past it holds an item of the next wave's group, whose quarter
+// and owner name a pod of this one, so this is the bound that matters; an item of a later tile of
+// the group is that pod's own evidence whenever it is ORed. A set wholly past the count is skipped
+// on a scalar branch. Containers (the word has no room for a quarter) stay per tile, into word
+// 4 * owner + j. After a wave barrier lane i reads its four pods' words with one 16-byte read and
+// the four tails run as in l6_scatter_tiles, restated here as there and to be kept in step.
+// A volume with several sources (KPE_L6T_VOL_ESC) is looked for once over the loaded sets; only
+// a group that may hold one takes the per-set ballots.
+template <bool SANN>
+__device__ __forceinline__ void l6_group_tiles() {
+  constexpr int T = 4;
+  extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
+  CBArgs& a = *(CBArgs*)kargs();
+  const uint32_t t = threadIdx.x, lane = t & 63u;
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const uint32_t gb = xcd_block(blockIdx.x, gridDim.x);
+  uint32_t lo = 0, hi = a.nshards;  // blk0[lo] <= gb < blk0[hi]
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a.blk0[mid] <= gb) lo = mid;
+    else hi = mid;
+  }
+  CShard& S = a.sh[lo];
+  const uint32_t n = S.n, ntiles = (n + 63u) >> 6;
+  const uint32_t tile0 = ((gb - a.blk0[lo]) * 4u + wv) * (uint32_t)T;
+  const uint32_t need = a.need;
+  const bool nvol = need & NEED_VOL, nsys = need & NEED_SYS, npann = need & NEED_PANN;
+  const Rsrc REC = make_rsrc(S.rec12, n * 4u);
+  const Rsrc HDR = make_rsrc(S.hdr, (ntiles + 1u) * 16u);
+  // the descriptor ends with the allocation (slack included): what a slot past the group's count
+  // holds is dropped by the count
+  const KpeL6TagLayout lay = kpe_l6_tag_layout(S.nctr, S.nvol, S.nsys, S.npann);
+  const Rsrc TAG = make_rsrc(S.cw4, (uint32_t)lay.bytes);
+  const uint32_t o_vol = (uint32_t)lay.o_vol, o_sys = (uint32_t)lay.o_sys, o_ann = (uint32_t)lay.o_ann;
+  const Rsrc SAN = make_rsrc(S.sann, SANN && (need & NEED_SANN) ? S.nctr * 4u : 0u);
+  const uint32_t l4 = lane * 4u;
+  auto ldt = [&](uint32_t voff, uint32_t soff) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(TAG, voff, soff, 0); };
+  // ---- step 1: headers and pod words. Lane k: word k & 3 of hdr[min(tile0 + k / 4, ntiles)]: a
+  // tile past the shard's end reads the sentinel, so it has no items and the group ends where the
+  // columns do
+  const uint32_t hl = min(lane, 4u * T + 3u);
+  const uint32_t hall = bload1(HDR, (min(tile0 + (hl >> 2), ntiles) * 4u + (hl & 3u)) * 4u);
+  uint32_t rec[T];
+#pragma unroll
+  for (int j = 0; j < T; ++j) rec[j] = bload1(REC, ((tile0 + j) * 64u + lane) * 4u);  // past n: zeros
+  const uint32_t nk = S.nkinds;
+  const uint32_t k0 = t < nk ? S.kt[t] : 0u;
+  const uint32_t ncw = (S.L.bytes + 3u) >> 2;
+  const uint32_t* gcw = reinterpret_cast<const uint32_t*>(S.codes);
+  const uint32_t cw0 = t < ncw ? gcw[t] : 0u;
+  const uint32_t* const gpt = a.pod_tab;
+  const uint32_t pt0 = gpt[t];
+  const uint32_t pt1 = t < KPE_L6_PT_WORDS - kLB ? gpt[t + kLB] : 0u;
+  // ---- step 2: every tile's containers, and the group's first sets of each list
+  const uint32_t V0 = hw(hall, 1u), S0 = hw(hall, 2u), A0 = hw(hall, 3u);
+  const uint32_t nvg = hw(hall, 4u * T + 1u) - V0, nsg = hw(hall, 4u * T + 2u) - S0, nag = hw(hall, 4u * T + 3u) - A0;
+  uint32_t c0[T], c1[T], a0[T], a1[T];
+#pragma unroll
+  for (int j = 0; j < T; ++j) {
+    if (tile0 + j >= ntiles) break;
+    const uint32_t C0 = hw(hall, 4u * j);
+    c0[j] = ldt(l4, C0 * 4u);
+    c1[j] = ldt(l4 + 256u, C0 * 4u);
+    if constexpr (SANN) {
+      a0[j] = bload1(SAN, (C0 + lane) * 4u);
+      a1[j] = bload1(SAN, (C0 + 64u + lane) * 4u);
+    }
+  }
+  uint32_t vw[KPE_L6G_VOL_SETS], sw_[KPE_L6G_SYS_SETS];
+  uint2 qw[KPE_L6G_ANN_SETS];
+#pragma unroll
+  for (uint32_t s = 0; s < KPE_L6G_VOL_SETS; ++s) vw[s] = nvol ? ldt(l4 + 256u * s, o_vol + V0 * 4u) : 0u;
+#pragma unroll
+  for (uint32_t s = 0; s < KPE_L6G_SYS_SETS; ++s) sw_[s] = nsys ? ldt(l4 + 256u * s, o_sys + S0 * 4u) : 0u;
+#pragma unroll
+  for (uint32_t s = 0; s < KPE_L6G_ANN_SETS; ++s) {
+    qw[s] = make_uint2(0u, 0u);
+    if (npann) {
+      const auto q = __builtin_amdgcn_raw_buffer_load_b64(TAG, lane * 8u + 512u * s, o_ann + A0 * 8u, 0);
+      qw[s] = make_uint2(q[0], q[1]);
+    }
+  }
+  dyn[t] = pt0;
+  if (t < KPE_L6_PT_WORDS - kLB) dyn[t + kLB] = pt1;
+  uint32_t* const kt = dyn + KPE_L6_PT_WORDS;
+  if (t < nk) kt[t] = k0;
+#pragma unroll 1
+  for (uint32_t i = t + kLB; i < nk; i += kLB) kt[i] = S.kt[i];
+  uint32_t* const cl = kt + a.kt_words;
+  if (t < ncw) cl[t] = cw0;
+#pragma unroll 1
+  for (uint32_t i = t + kLB; i < ncw; i += kLB) cl[i] = gcw[i];
+  const uint32_t ncls = a.ncls;
+  // the wave's 256 evidence words (16 bytes per lane: its four pods'), then the rows
+  uint8_t* const stg = reinterpret_cast<uint8_t*>(cl + a.code_words + wv * a.wave_words);
+  uint32_t* const acc = reinterpret_cast<uint32_t*>(stg);
+  reinterpret_cast<uint4*>(stg)[lane] = make_uint4(0u, 0u, 0u, 0u);
+  uint8_t* const sv = stg + KPE_L6G_ACC_BYTES;  // a tile's verdict rows (64 x R bytes; 256 at least)
+  __syncthreads();
+  const uint8_t* const lcodes = reinterpret_cast<const uint8_t*>(cl);
+  auto cb = [&](uint32_t i) -> uint32_t { return (uint32_t)lcodes[i]; };
+  PsaCodes L;
+  L.ncapsets = S.L.ncapsets, L.nsysd = S.L.nsysd, L.nannk = S.L.nannk, L.nannv = S.L.nannv;
+  L.o_sys = S.L.o_sys, L.o_annk = S.L.o_annk, L.o_annv = S.L.o_annv, L.bytes = S.L.bytes;
+  const PsaCoder K{L};
+  uint32_t cev[KPE_L6_CLS], cev_nw[KPE_L6_CLS], crm[KPE_L6_CLS];
+#pragma unroll
+  for (uint32_t c = 0; c < KPE_L6_CLS; ++c) {
+    cev[c] = a.cls_ev[c], cev_nw[c] = a.cls_ev_nw[c], crm[c] = a.cls_rm[c];
+    asm volatile("" : "+s"(cev[c]), "+s"(cev_nw[c]), "+s"(crm[c]));
+  }
+  const uint32_t R = a.nrules, pss_rules = a.pss_rules;
+  const uint32_t ep_rules = a.err_rules | a.pat_rules, pat_rules = a.pat_rules;
+  const bool rpack = R - 2u <= 2u;  // rows of 2 to 4 bytes leave as one dword store per lane (as in the gather form)
+  uint32_t rp_cell = 0, rp_sel = 0;
+  if (rpack) {
+    const uint32_t b = 4u * lane, p0 = R == 3u ? (b * 171u) >> 9 : b >> (R >> 1), r0 = b - p0 * R;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+      const uint32_t g = r0 + k;
+      rp_sel |= (g >= R ? 4u + g - R : g) << (8u * k);
+    }
+    rp_cell = min(p0, 63u);
+  }
+  // evidence `ev` of the list item whose first word is w, into its pod's word (byte 3 of w: 4 *
+  // owner + quarter); 0 from a slot that is no item of the group
+  auto put = [&](uint32_t w, uint32_t ev, bool valid) {
+    __hip_atomic_fetch_or(acc + kpe_l6_tag_slot(w), valid ? ev : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+  };
+  auto ctr_ev = [&](uint32_t e, uint32_t cs) -> uint32_t {
+    uint32_t w = (e & ((1u << KPE_L6C_STATES) - 1u)) | ((cb(kpe_l6_ctr_capset(e)) & 7u) << KPE_L6C_CAP_SH);
+    if constexpr (SANN) w |= K.sann(cb, cs) << KPE_L6C_SANN_SH;
+    return w;
+  };
+  // ---- containers, per tile: slots lane and 64 + lane, then batches of 64; tile j's into word 4 * owner + j
+#pragma unroll
+  for (int j = 0; j < T; ++j) {
+    if (tile0 + j >= ntiles) break;
+    const uint32_t C0 = hw(hall, 4u * j), nct = hw(hall, 4u * j + 4u) - C0;
+    auto putc = [&](uint32_t w, uint32_t ev, bool valid) {
+      __hip_atomic_fetch_or(acc + 4u * kpe_l6_tag_owner(w) + (uint32_t)j, valid ? ev : 0u, __ATOMIC_RELAXED,
+                            __HIP_MEMORY_SCOPE_WAVEFRONT);
+    };
+    putc(c0[j], ctr_ev(c0[j], SANN ? a0[j] : 0u), lane < nct);
+    putc(c1[j], ctr_ev(c1[j], SANN ? a1[j] : 0u), lane + 64u < nct);
+#pragma unroll 1
+    for (uint32_t b = KPE_L6_CTR; b < nct; b += 64u) {
+      const uint32_t e = ldt(l4, (C0 + b) * 4u);
+      const uint32_t cs = SANN ? bload1(SAN, (C0 + b + lane) * 4u) : 0u;
+      putc(e, ctr_ev(e, cs), b + lane < nct);
+    }
+  }
+  // ---- the group's lists
+  if (nvol && nvg) {
+    // the volume decision with the per-set look for a volume of several sources: vol_code of its
+    // original mask
+    auto vol_ev = [&](uint32_t w, uint32_t slot) -> uint32_t {
+      uint32_t c = kpe_l6_vol_decide(w);
+      const bool esc = slot < nvg && (w & KPE_L6T_VOL_ESC);
+      if (__builtin_amdgcn_ballot_w64(esc)) {
+        if (esc) c = vol_code(S.vol[V0 + slot]);
+      }
+      return c << KPE_L6C_VOL_SH;
+    };
+    // one look over the loaded sets (a slot past the count may hold the next group's: then the
+    // per-set path runs for nothing)
+    uint32_t any = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < KPE_L6G_VOL_SETS; ++s) any |= vw[s];
+    if (!__builtin_amdgcn_ballot_w64((any & KPE_L6T_VOL_ESC) != 0u)) {
+#pragma unroll
+      for (uint32_t s = 0; s < KPE_L6G_VOL_SETS; ++s)
+        if (64u * s < nvg) put(vw[s], kpe_l6_vol_decide(vw[s]) << KPE_L6C_VOL_SH, 64u * s + lane < nvg);
+    } else {
+#pragma unroll
+      for (uint32_t s = 0; s < KPE_L6G_VOL_SETS; ++s)
+        if (64u * s < nvg) put(vw[s], vol_ev(vw[s], 64u * s + lane), 64u * s + lane < nvg);
+    }
+#pragma unroll 1
+    for (uint32_t b = 64u * KPE_L6G_VOL_SETS; b < nvg; b += 64u) {
+      const uint32_t w = ldt(l4, o_vol + (V0 + b) * 4u);
+      put(w, vol_ev(w, b + lane), b + lane < nvg);
+    }
+  }
+  if (nsys && nsg) {
+#pragma unroll
+    for (uint32_t s = 0; s < KPE_L6G_SYS_SETS; ++s)
+      if (64u * s < nsg) put(sw_[s], K.sys(cb, kpe_l6_tag_get_id(sw_[s])) << KPE_L6C_SYS_SH, 64u * s + lane < nsg);
+#pragma unroll 1
+    for (uint32_t b = 64u * KPE_L6G_SYS_SETS; b < nsg; b += 64u) {
+      const uint32_t w = ldt(l4, o_sys + (S0 + b) * 4u);
+      put(w, K.sys(cb, kpe_l6_tag_get_id(w)) << KPE_L6C_SYS_SH, b + lane < nsg);
+    }
+  }
+  if (npann && nag) {
+#pragma unroll
+    for (uint32_t s = 0; s < KPE_L6G_ANN_SETS; ++s)
+      if (64u * s < nag)
+        put(qw[s].x, K.ann(cb, make_uint2(kpe_l6_tag_get_id(qw[s].x), qw[s].y)) << KPE_L6C_ANN_SH, 64u * s + lane < nag);
+#pragma unroll 1
+    for (uint32_t b = 64u * KPE_L6G_ANN_SETS; b < nag; b += 64u) {
+      const auto q = __builtin_amdgcn_raw_buffer_load_b64(TAG, lane * 8u, o_ann + (A0 + b) * 8u, 0);
+      put(q[0], K.ann(cb, make_uint2(kpe_l6_tag_get_id(q[0]), q[1])) << KPE_L6C_ANN_SH, b + lane < nag);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  const uint4 cw4 = reinterpret_cast<const uint4*>(stg)[lane];
+  const uint32_t cws[T] = {cw4.x, cw4.y, cw4.z, cw4.w};
+#pragma unroll
+  for (int j = 0; j < T; ++j) {
+    const uint32_t tile = tile0 + j;
+    if (tile >= ntiles) break;
+    const uint32_t r = tile * 64u + lane;
+    const bool live = r < n;
+    const uint32_t cw = cws[j];
+    // ---- the version classes, the rule match (kind table) and the verdict bytes: as the gather form
+    uint32_t failr = 0;
+    const uint32_t w = rec[j];
+    const uint32_t tw = kpe_l6p_pod_lookup(dyn, w), cls = kpe_l6p_class(w), kind = kpe_l6p_kind(w);
+    const bool derr = w & KPE_L6P_DECODE_ERR;
+    const uint32_t ev = kpe_l6c_pod_split(cw, tw, 0u);
+    const uint32_t ev_nw = ev & (uint32_t)((int32_t)tw >> 31);  // KPE_L6_PT_NW over the word
+#pragma unroll
+    for (uint32_t c = 0; c < KPE_L6_CLS; ++c) {
+      if (c >= ncls) break;
+      const uint32_t hit = (ev & cev[c]) | (ev_nw & cev_nw[c]);
+      uint32_t m = hit ? ~0u : 0u;
+      asm("" : "+v"(m));  // keeps the select on inline constants (see the gather form)
+      failr |= m & crm[c];
+    }
+    const bool err = cls == R_CLASS_OTHER || derr;
+    const uint32_t matched = live && kind < nk ? kt[kind] : 0u;
+    const uint32_t E = matched & ((err ? pss_rules : 0u) | ep_rules);
+    const uint32_t F = (matched & pss_rules & failr & ~E) | (matched & pat_rules);  // F|E = PENDING
+    const uint32_t P = matched & pss_rules & ~failr & ~E;
+    const uint32_t nrows = min(64u, n - tile * 64u);
+    bool stored = false;
+    if (R <= 4u) {  // the row as one word, byte ri = rule ri's cell
+      constexpr uint32_t kSpread = 0x204081u, kOnes = 0x01010101u;
+      const uint32_t cellw = (__umul24(P, kSpread) & kOnes) | (__umul24(F, kSpread << 1) & (kOnes << 1)) |
+                             (__umul24(E, kSpread << 2) & (kOnes << 2));
+      if (rpack && nrows == 64u) {
+        uint32_t* const sw = reinterpret_cast<uint32_t*>(sv);
+        sw[lane] = cellw;
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t w0 = sw[rp_cell], w1 = sw[min(rp_cell + 1u, 63u)];
+        if (lane < 16u * R)
+          reinterpret_cast<uint32_t*>(S.verdicts + (size_t)tile * (64u * R))[lane] = __builtin_amdgcn_perm(w1, w0, rp_sel);
+        stored = true;
+      } else {
+#pragma unroll
+        for (uint32_t ri = 0; ri < 4u; ++ri)
+          if (ri < R) sv[lane * R + ri] = (uint8_t)(cellw >> (8u * ri));
+      }
+    } else {
+#pragma unroll 1
+      for (uint32_t ri = 0; ri < R; ++ri)
+        sv[lane * R + ri] = (uint8_t)(((P >> ri) & 1u) | (((F >> ri) & 1u) << 1) | (((E >> ri) & 1u) << 2));
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (!stored) store_rows(S.verdicts, sv, tile, R, 0, R, nrows, lane);
+    __builtin_amdgcn_wave_barrier();  // the rows are read before the next tile's are written
+  }
+}
+
 // SC: the scatter form of CP over the corpus's owner-tagged columns (l6_scatter_tiles); each
 // instantiation holds the one body it runs.
-// NW: its narrow form, over the pod word column (T >= 2).
-template <int T, bool LC, bool SANN, bool CV, bool CP = false, bool SC = false, bool NW = false>
+// NW: its narrow form, over the pod word column (T >= 2). GR: the group form of that (T = 4).
+template <int T, bool LC, bool SANN, bool CV, bool CP = false, bool SC = false, bool NW = false, bool GR = false>
 __global__ void __launch_bounds__(kLB, l6_waves(SANN, CP)) __attribute__((amdgpu_num_sgpr(KPE_LEAN6_SGPRS)))
 kpe_lean6_kernel(LeanBatchArgs) {
   static_assert(!(CP && CV), "the compact columns are read by the verdict-only form");
   static_assert(!SC || (CP && LC), "the scatter form is a compact form with the code bytes in LDS");
   static_assert(!NW || (SC && T >= 2), "the narrow form is a scatter form of two or four tiles per wave");
-  if constexpr (SC) l6_scatter_tiles<T, SANN, NW>();
+  static_assert(!GR || (NW && T == 4), "the group form is the narrow form at four tiles per wave");
+  if constexpr (GR) l6_group_tiles<SANN>();
+  else if constexpr (SC) l6_scatter_tiles<T, SANN, NW>();
   else l6_gather_tiles<T, LC, SANN, CV, CP>();
 }

@@ -1257,12 +1257,20 @@ extern "C" hipError_t kpe_launch_selmask(const SelMaskArgs* a, hipStream_t s) {
 // cp: the verdict-only form reads the compact columns (LeanShard::rec12 / cw4; class masks and pod
 // table in the packed numbering); kpe_lean6_compact says which launches may ask for it. cp == 2:
 // the scatter form over the owner-tagged columns (SC; LeanShard::cw4 is their base). cp == 3
-// (tpw 2 or 4 only): its narrow form (NW; LeanShard::rec12 is the pod word column pw4).
+// (tpw 2 or 4 only): its narrow form (NW; LeanShard::rec12 is the pod word column pw4). cp == 4
+// (tpw 4 only): the group form of the narrow form (GR; wave_words holds KPE_L6G_ACC_BYTES and the rows).
 template <int T, bool LC>
 static void lean6_go(int sann, int cv, int cp, dim3 g, dim3 b, size_t dyn_bytes, hipStream_t s, const LeanBatchArgs& a) {
   if constexpr (!LC) {
     hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, true>), g, b, dyn_bytes, s, a);
   } else {
+    if constexpr (T == 4) {
+      if (cp == 4) {
+        if (sann) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, false, true, true, true, true>), g, b, dyn_bytes, s, a);
+        else hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, false, false, true, true, true, true>), g, b, dyn_bytes, s, a);
+        return;
+      }
+    }
     if constexpr (T >= 2) {
       if (cp == 3) {
         if (sann) hipLaunchKernelGGL((kpe_lean6_kernel<T, LC, true, false, true, true, true>), g, b, dyn_bytes, s, a);
@@ -1288,6 +1296,8 @@ extern "C" hipError_t kpe_launch_lean6(const LeanBatchArgs* a, size_t dyn_bytes,
   if (!cv && a->ncls > KPE_L6_CLS) return hipErrorInvalidValue;
   if (cp && !kpe_lean6_compact(lc, cv)) return hipErrorInvalidValue;
   if (cp == 3 && a->tpw < 2) return hipErrorInvalidValue;
+  if (cp == 4 && a->tpw != 4) return hipErrorInvalidValue;
+  if (cp < 0 || cp > 4) return hipErrorInvalidValue;
   const dim3 g(grid), b(kLB);
   if (a->tpw == 4 && lc) lean6_go<4, true>(sann, cv, cp, g, b, dyn_bytes, s, *a);
   else if (a->tpw == 2 && lc) lean6_go<2, true>(sann, cv, cp, g, b, dyn_bytes, s, *a);
