@@ -236,6 +236,39 @@ kpe_status kpe_corpus_set_namespace_labels(kpe_device* dev, kpe_corpus* c, const
  * back with KPE_NSL_REPLACE it rebuilds the same table): writes at most cap bytes into out (no
  * terminator) and returns the length needed, or -kpe_status. Host only. */
 int64_t kpe_corpus_namespace_labels(const kpe_corpus* c, char* out, size_t cap);
+/* A corpus out of chosen rows of other corpora (host only, no JSON is read): pairs is npairs x
+ * {src, row}, and row k of *out is row `row` of srcs[src]. Every consumer behaves as on a corpus
+ * flattened from the listed rows' NDJSON lines, in list order, under the sources' namespace label
+ * table: evaluation in every form (verdicts, check masks, counts), namespace counts, row flags,
+ * exclusions, traces, report rows and fingerprints. *out is not uploaded, has nothing retired and
+ * keeps nothing. Runs on the flattener's threads.
+ * Ids: the sources' dictionaries, scalar tables and capability sets are merged whole, in source
+ * order, first occurrence first (the parallel flattener's rule). When every row of every source is
+ * listed in source order the ids are those of a sequential flatten: for sources that are consecutive
+ * chunks of one NDJSON, kpe_corpus_digest(*out) equals the digest of flattening the whole input. For
+ * any other list the digest may differ (strings only dropped rows used stay in the dictionaries, so
+ * a namespace group without rows may exist where a fresh flatten has none); no consumer sees ids.
+ * Rows: a row listed twice appears twice. A row that is KPE_ROW_LIMIT in its source stays so (some
+ * limits depend on the source's dictionaries; KPE_UNDECIDED is the safe side), so equality with a
+ * fresh flatten holds for rows not past a limit in their source. The decode-error, no-spec and
+ * context-error flags travel with the row.
+ * KPE_E_INVALID: a null argument or nsrcs < 1; a pair outside its source or naming a retired row;
+ * sources that differ in KPE_CORPUS_DOCS; sources whose namespace label tables differ (compared by
+ * namespace, as sets of pairs). KPE_E_LIMIT: the merged dictionaries or capability sets cross a
+ * corpus-wide or per-resource limit the sources' rows were flattened under, or a column outgrows its
+ * 32-bit offsets: flatten the lines again. On any error *out is untouched. */
+kpe_status kpe_corpus_gather(const kpe_corpus* const* srcs, int nsrcs, const uint64_t* pairs, uint64_t npairs,
+                             kpe_corpus** out);
+/* One 64-bit digest per row that holds no id and no position (host only; out: N words): every
+ * dictionary id stands by its string, a GVK by its three strings, a capability mask by its names, a
+ * capability-set id by its (add, drop) sets, a scalar id by its type, value bits and texts, the row's
+ * label-table row by that namespace's label pairs as a set, and the document tape is walked from the
+ * row's root and its `images` root with every kind and count word. Two corpora give a row the same
+ * digest whenever it was flattened from the same line under the same label table, whatever else they
+ * hold; it changes when any word of the row that the kernels, the exclusion pass, the traces or the
+ * reports read changes. The check of kpe_corpus_gather, and a diagnostic for a resident corpus
+ * against its NDJSON. */
+kpe_status kpe_corpus_row_digests(const kpe_corpus* c, uint64_t* out);
 /* The corpus's per-pod PSA summary, built on dev (waits for it; builds it first when no LEAN
  * evaluation has yet): 2 words per row (include-free layout of kyverno_amd/csrc/schema.h PS_*:
  * x = OR of the pod's container state bitmaps, y = the list codes under the PSA library's fixed
@@ -546,6 +579,22 @@ kpe_status kpe_fingerprints_load(kpe_device* dev, kpe_corpus* c, const uint64_t*
 kpe_status kpe_fingerprints_fetch(kpe_device* dev, const kpe_corpus* c, uint64_t row0, uint64_t nrows, uint64_t* out);
 kpe_status kpe_fingerprints_drop(kpe_device* dev, kpe_corpus* c);
 int kpe_fingerprints_kept(const kpe_corpus* c); /* 0 or 1 */
+/* Carry kept results into a gathered corpus (kpe_corpus_gather), on the device: dst, uploaded to dev
+ * with npairs rows, receives as its kept matrix (KPE_GATHER_MATRIX) row k = kept row `row` of
+ * srcs[src], with the sources' R and rule names, and as its kept fingerprints
+ * (KPE_GATHER_FINGERPRINTS) the 8 bytes of the same rows; what == 0 carries whatever every listed
+ * source keeps (possibly nothing). A source is listed when a pair names it (every source when
+ * npairs == 0). No evaluation and no program are involved; whatever dst kept of a requested kind is
+ * replaced. The copy is ordered after each listed source's pending kpe_results_keep /
+ * kpe_fingerprints_keep and before dst's next evaluation; the call waits for it.
+ * KPE_E_INVALID: a null argument, nsrcs < 1, an unknown bit of what, npairs other than dst's rows, dst
+ * among the sources, a pair outside its source or naming a retired row. KPE_E_STATE: dst or a source
+ * is not uploaded to dev; a listed source keeps nothing of a requested kind; the kept rule names of
+ * the listed sources differ in count, order or text. All checked before any device call. */
+#define KPE_GATHER_MATRIX 1u
+#define KPE_GATHER_FINGERPRINTS 2u
+kpe_status kpe_results_gather(kpe_device* dev, kpe_corpus* dst, const kpe_corpus* const* srcs, int nsrcs,
+                              const uint64_t* pairs, uint64_t npairs, uint32_t what);
 /* The rows whose fingerprint under the last evaluation of prog differs from the kept one, ascending:
  * the first min(total, cap) row indices into rows[], and, when not NULL, those rows of the new matrix
  * (R bytes each) into verdict_rows[] and their new fingerprints into fps_out[]; memory past that is

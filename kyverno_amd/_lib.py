@@ -152,6 +152,12 @@ def load():
     L.kpe_corpus_set_namespace_labels.restype = ctypes.c_int
     L.kpe_corpus_namespace_labels.argtypes = [vp, vp, ctypes.c_size_t]
     L.kpe_corpus_namespace_labels.restype = i64
+    L.kpe_corpus_gather.argtypes = [vp, i32, vp, u64, ctypes.POINTER(vp)]
+    L.kpe_corpus_gather.restype = ctypes.c_int
+    L.kpe_corpus_row_digests.argtypes = [vp, vp]
+    L.kpe_corpus_row_digests.restype = ctypes.c_int
+    L.kpe_results_gather.argtypes = [vp, vp, vp, i32, vp, u64, u32]
+    L.kpe_results_gather.restype = ctypes.c_int
     L.kpe_changed_pairs.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64]
     L.kpe_changed_pairs.restype = i64
     L.kpe_changed_pairs_fp.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, u8, u32, vp, vp, vp, u64]

@@ -61,6 +61,26 @@ inline const NsGroups& ns_groups(const kpe_corpus* c) {
   }
   return *c->ns;
 }
+// The argument checks kpe_corpus_gather and kpe_results_gather share: non-null sources, every pair
+// inside its source and on a row that is not retired. listed[t] (when not null): a pair names
+// source t, or there is no pair at all.
+inline kpe_status gather_args(const char* who, const kpe_corpus* const* srcs, int nsrcs, const uint64_t* pairs,
+                              uint64_t npairs, std::vector<uint8_t>* listed) {
+  const std::string w(who);
+  if (!srcs || nsrcs < 1 || (npairs && !pairs)) return fail(KPE_E_INVALID, w + ": null argument");
+  for (int t = 0; t < nsrcs; ++t)
+    if (!srcs[t]) return fail(KPE_E_INVALID, w + ": null source");
+  if (listed) listed->assign((size_t)nsrcs, npairs ? 0 : 1);
+  for (uint64_t k = 0; k < npairs; ++k) {
+    const uint64_t t = pairs[2 * k], r = pairs[2 * k + 1];
+    if (t >= (uint64_t)nsrcs || r >= (uint64_t)srcs[t]->c->n) return fail(KPE_E_INVALID, w + ": a pair outside its source");
+    const auto& ret = srcs[t]->retired;
+    if (!ret.empty() && std::binary_search(ret.begin(), ret.end(), (uint32_t)r))
+      return fail(KPE_E_INVALID, w + ": a pair names a retired row");
+    if (listed) (*listed)[t] = 1;
+  }
+  return KPE_OK;
+}
 }  // namespace kpe
 
 #ifdef KPE_API_HIP

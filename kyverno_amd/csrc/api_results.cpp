@@ -1028,6 +1028,80 @@ kpe_status kpe_fingerprints_drop(kpe_device* dev, kpe_corpus* c) {
 
 int kpe_fingerprints_kept(const kpe_corpus* c) { return c && c->d && c->d->fps_kept ? 1 : 0; }
 
+// ---- kept results carried into a gathered corpus ------------------------------------------------
+kpe_status kpe_results_gather(kpe_device* dev, kpe_corpus* dst, const kpe_corpus* const* srcs, int nsrcs,
+                              const uint64_t* pairs, uint64_t npairs, uint32_t what) {
+  if (!dev || !dst) return fail(KPE_E_INVALID, "kpe_results_gather: null argument");
+  if (what & ~(KPE_GATHER_MATRIX | KPE_GATHER_FINGERPRINTS)) return fail(KPE_E_INVALID, "kpe_results_gather: unknown flag");
+  std::vector<uint8_t> listed;
+  if (kpe_status st = kpe::gather_args("kpe_results_gather", srcs, nsrcs, pairs, npairs, &listed)) return st;
+  if (npairs != (uint64_t)dst->c->n) return fail(KPE_E_INVALID, "kpe_results_gather: one pair per row of dst");
+  for (int t = 0; t < nsrcs; ++t)
+    if (srcs[t] == dst) return fail(KPE_E_INVALID, "kpe_results_gather: dst is among the sources");
+  std::lock_guard<std::mutex> lk(dev->mu);  // the corpora's device state is read under the lock
+  if (!dst->d || dst->d->ordinal != dev->ordinal) return fail(KPE_E_STATE, "kpe_results_gather: dst is not uploaded to this device");
+  for (int t = 0; t < nsrcs; ++t)
+    if (!srcs[t]->d || srcs[t]->d->ordinal != dev->ordinal)
+      return fail(KPE_E_STATE, "kpe_results_gather: a source is not uploaded to this device");
+  // what every listed source keeps; the first listed source's names are the reference
+  bool all_m = true, all_f = true;
+  const kpe::DeviceCorpus* first = nullptr;
+  for (int t = 0; t < nsrcs; ++t) {
+    if (!listed[t]) continue;
+    const kpe::DeviceCorpus& S = *srcs[t]->d;
+    all_m = all_m && S.kept_rules >= 0, all_f = all_f && S.fps_kept;
+    if (!first) first = &S;
+  }
+  if ((what & KPE_GATHER_MATRIX) && !all_m) return fail(KPE_E_STATE, "kpe_results_gather: a listed source keeps no matrix");
+  if ((what & KPE_GATHER_FINGERPRINTS) && !all_f)
+    return fail(KPE_E_STATE, "kpe_results_gather: a listed source keeps no fingerprints");
+  if (!what) what = (all_m ? KPE_GATHER_MATRIX : 0u) | (all_f ? KPE_GATHER_FINGERPRINTS : 0u);
+  if (what & KPE_GATHER_MATRIX)
+    for (int t = 0; t < nsrcs; ++t)
+      if (listed[t] && (srcs[t]->d->kept_rules != first->kept_rules || srcs[t]->d->kept_names != first->kept_names))
+        return fail(KPE_E_STATE, "kpe_results_gather: the listed sources' kept rule names differ");
+  if (!what) return KPE_OK;
+  HIPCHK(hipSetDevice(dev->ordinal));
+  kpe::DeviceCorpus& D = *dst->d;
+  // behind every listed source's pending keep (enqueued on the stream of its last evaluation)
+  for (int t = 0; t < nsrcs; ++t)
+    if (listed[t]) HIPCHK(hipStreamSynchronize(srcs[t]->d->bind.last ? srcs[t]->d->bind.last : dev->stream));
+  hipStream_t s = D.bind.last ? D.bind.last : dev->stream;
+  // this call's scratch: the pair list, then one base pointer per source and kind
+  const size_t pair_bytes = (size_t)npairs * 16, tab_bytes = (size_t)nsrcs * 8;
+  DevBuf scratch;
+  HIPCHK(scratch.ensure(pair_bytes + 2 * tab_bytes));
+  uint64_t* d_pairs = scratch.as<uint64_t>();
+  std::vector<const void*> tab(2 * (size_t)nsrcs, nullptr);
+  for (int t = 0; t < nsrcs; ++t) {
+    if (!listed[t]) continue;
+    if (what & KPE_GATHER_MATRIX) tab[t] = srcs[t]->d->kept.p;
+    if (what & KPE_GATHER_FINGERPRINTS) tab[(size_t)nsrcs + t] = srcs[t]->d->fps.p;
+  }
+  if (npairs) HIPCHK(hipMemcpyAsync(d_pairs, pairs, pair_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(scratch.as<uint8_t>() + pair_bytes, tab.data(), 2 * tab_bytes, hipMemcpyHostToDevice, s));
+  const uint8_t* const* d_tab_m = reinterpret_cast<const uint8_t* const*>(scratch.as<uint8_t>() + pair_bytes);
+  const uint64_t* const* d_tab_f = reinterpret_cast<const uint64_t* const*>(scratch.as<uint8_t>() + pair_bytes + tab_bytes);
+  if (what & KPE_GATHER_MATRIX) {
+    const size_t R = (size_t)first->kept_rules;
+    D.kept_rules = -1;
+    D.splice_valid = false;
+    HIPCHK(D.kept.ensure((size_t)npairs * R));
+    HIPCHK(kpe_launch_results_gather(d_tab_m, d_pairs, npairs, (uint32_t)R, D.kept.as<uint8_t>(), s));
+    D.kept_names = first->kept_names;
+    D.kept_rules = (int64_t)R;
+  }
+  if (what & KPE_GATHER_FINGERPRINTS) {
+    D.fps_kept = false;
+    HIPCHK(D.fps.ensure((size_t)npairs * 8));
+    HIPCHK(kpe_launch_fp_gather_pairs(d_tab_f, d_pairs, npairs, D.fps.as<uint64_t>(), s));
+    D.fps_tbl.clear();
+    D.fps_kept = true;
+  }
+  HIPCHK(hipStreamSynchronize(s));  // the scratch and the caller's pairs are this call's
+  return KPE_OK;
+}
+
 static kpe_status changed_fp_impl(kpe_device* dev, const kpe_program* prog, const kpe_corpus* c, const uint64_t* salts,
                                   const uint64_t* msg_salts, uint8_t msg_codes, uint32_t flags, uint64_t* rows_out,
                                   uint8_t* vrows_out, uint64_t* fps_out, uint64_t cap, uint64_t* total_out) {

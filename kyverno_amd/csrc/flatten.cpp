@@ -20,6 +20,7 @@
 #include <string>
 #include <atomic>
 #include <functional>
+#include <map>
 #include <thread>
 #include <vector>
 
@@ -1879,14 +1880,14 @@ void parallel_for(size_t n, unsigned nth, F f) {
 // then number their first occurrences in local order after G's size plus the earlier parts'
 // counts, references take their first occurrence's id, the bytes are appended per part, and the
 // index is rebuilt in parallel (Dict::reindex). dmap[t][d][i]: G id of part t's string i.
-void merge_dict_parallel(Dict& G, std::vector<Corpus>& parts, int d,
+void merge_dict_parallel(Dict& G, const std::vector<const Corpus*>& parts, int d,
                          std::vector<std::vector<std::vector<uint32_t>>>& dmap, unsigned nth) {
   const size_t T = parts.size();
   constexpr uint32_t kB = 64, kFirst = 0xFFFFFFFEu, kRef = 0xFFFFFFFDu;
   std::vector<std::vector<uint64_t>> hs(T), ref(T);
   std::vector<std::vector<std::vector<uint32_t>>> lists(T, std::vector<std::vector<uint32_t>>(kB));
   parallel_for(T, nth, [&](size_t t) {
-    const Dict& D = parts[t].dict[d];
+    const Dict& D = parts[t]->dict[d];
     hs[t].resize(D.size());
     ref[t].assign(D.size(), ~0ull);
     dmap[t][d].assign(D.size(), kFirst);
@@ -1905,7 +1906,7 @@ void merge_dict_parallel(Dict& G, std::vector<Corpus>& parts, int d,
     std::vector<uint64_t> tab(cap, ~0ull);  // first occurrences: t << 32 | i
     const size_t mask = cap - 1;
     for (size_t t = 0; t < T; ++t) {
-      const Dict& D = parts[t].dict[d];
+      const Dict& D = parts[t]->dict[d];
       for (uint32_t i : lists[t][b]) {
         const std::string_view sv = D.at(i);
         const uint64_t h = hs[t][i];
@@ -1924,7 +1925,7 @@ void merge_dict_parallel(Dict& G, std::vector<Corpus>& parts, int d,
           }
           const size_t t0 = (size_t)(e >> 32);
           const uint32_t i0 = (uint32_t)e;
-          if (hs[t0][i0] == h && parts[t0].dict[d].at(i0) == sv) {
+          if (hs[t0][i0] == h && parts[t0]->dict[d].at(i0) == sv) {
             ref[t][i] = e;
             dmap[t][d][i] = kRef;
             break;
@@ -1937,7 +1938,7 @@ void merge_dict_parallel(Dict& G, std::vector<Corpus>& parts, int d,
   std::vector<size_t> nf(T, 0), nb(T, 0);
   std::vector<std::vector<uint8_t>> first(T);
   parallel_for(T, nth, [&](size_t t) {
-    const Dict& D = parts[t].dict[d];
+    const Dict& D = parts[t]->dict[d];
     first[t].assign(D.size(), 0);
     for (uint32_t i = 0; i < D.size(); ++i)
       if (dmap[t][d][i] == kFirst) first[t][i] = 1, ++nf[t], nb[t] += D.at(i).size();
@@ -1949,7 +1950,7 @@ void merge_dict_parallel(Dict& G, std::vector<Corpus>& parts, int d,
   G.bytes.resize(byb[T]);
   G.off.resize(idb[T] + 1);
   parallel_for(T, nth, [&](size_t t) {
-    const Dict& D = parts[t].dict[d];
+    const Dict& D = parts[t]->dict[d];
     uint32_t id = (uint32_t)idb[t];
     size_t pos = byb[t];
     for (uint32_t i = 0; i < D.size(); ++i) {
@@ -2018,18 +2019,33 @@ void Dict::reindex(const std::vector<uint64_t>& hs, unsigned nth) {
 
 namespace {
 
-// Concatenate per-chunk corpora (flattened in parallel, each with its own dictionaries) into
-// C. Parts are merged in document order, so every dictionary, scalar and capability-set id
-// is the one a sequential flatten assigns (first occurrence order).
-void merge_parts(Corpus& C, std::vector<Corpus>& parts, bool docs, unsigned nthreads) {
+// The id maps of a merge: part t's dictionary id i of domain d, capability set j and scalar k in
+// the merged corpus. merge_parts (whole parts) and gather_rows (chosen rows) place through them.
+struct IdMaps {
+  std::vector<std::vector<std::vector<uint32_t>>> dmap;  // [t][d][i]
+  std::vector<std::vector<uint32_t>> capmap, scmap;      // [t][j], [t][k]
+};
+
+uint64_t capbits(uint64_t m, const std::vector<uint32_t>& cm) {
+  uint64_t o = 0;
+  for (; m; m &= m - 1) o |= 1ull << cm[__builtin_ctzll(m)];
+  return o;
+}
+
+// Merge the dictionaries, scalar tables (docs) and capability sets of the parts into C's, parts in
+// order, first occurrence first (the ids a sequential flatten assigns), and fill M. Throws
+// NeedSequential / LimitError when the merged tables cross a corpus-wide limit.
+void merge_ids(Corpus& C, const std::vector<const Corpus*>& parts, bool docs, unsigned nthreads, IdMaps& M) {
   const size_t T = parts.size();
-  const auto tm0 = std::chrono::steady_clock::now();
-  // ---- id maps (sequential, document order) ----
-  std::vector<std::vector<std::vector<uint32_t>>> dmap(T, std::vector<std::vector<uint32_t>>(KPE_NUM_DOMAINS));
-  std::vector<std::vector<uint32_t>> capmap(T), scmap(T);
+  M.dmap.assign(T, std::vector<std::vector<uint32_t>>(KPE_NUM_DOMAINS));
+  M.capmap.assign(T, {}), M.scmap.assign(T, {});
+  auto& dmap = M.dmap;
+  auto& capmap = M.capmap;
+  auto& scmap = M.scmap;
   auto merge_scalars = [&] {  // scalar tables (document tapes), parts in document order
     for (size_t t = 0; t < T; ++t) {
-      const Corpus& P = parts[t];
+      const Corpus& P = *parts[t];
+      if (P.scal.empty()) continue;  // a part without rows built no table
       if (C.scal.empty()) C.scal.assign(P.scal.begin(), P.scal.begin() + 3), C.scal_text.assign(P.scal_text.begin(), P.scal_text.begin() + 9);
       auto& sm = scmap[t];
       sm.resize(P.scal.size());
@@ -2088,7 +2104,7 @@ void merge_parts(Corpus& C, std::vector<Corpus>& parts, bool docs, unsigned nthr
     for (int d = 0; d < KPE_NUM_DOMAINS; ++d)
       th.emplace_back([&, d] {
         size_t tot = C.dict[d].size();
-        for (size_t t = 0; t < T; ++t) tot += parts[t].dict[d].size();
+        for (size_t t = 0; t < T; ++t) tot += parts[t]->dict[d].size();
         if (tot >= (1u << 16) && nthreads > 1) {  // e.g. resource names (one per resource)
           try {
             merge_dict_parallel(C.dict[d], parts, d, dmap, nthreads);
@@ -2099,7 +2115,7 @@ void merge_parts(Corpus& C, std::vector<Corpus>& parts, bool docs, unsigned nthr
         }
         C.dict[d].reserve(tot);
         for (size_t t = 0; t < T; ++t) {
-          const Dict& D = parts[t].dict[d];
+          const Dict& D = parts[t]->dict[d];
           auto& m = dmap[t][d];
           m.resize(D.size());
           for (uint32_t i = 0; i < D.size(); ++i) m[i] = C.dict[d].intern(D.at(i));
@@ -2110,20 +2126,14 @@ void merge_parts(Corpus& C, std::vector<Corpus>& parts, bool docs, unsigned nthr
     for (auto& e : derr)
       if (e) std::rethrow_exception(e);
   }
-  const auto tm1 = std::chrono::steady_clock::now();
   // per-resource limits decided against one part's dictionaries may differ from the merged
   // ones: such a corpus is flattened again on one thread
   if (C.dict[D_CAP].size() > 64 || C.dict[D_KIND].size() > 4096 || C.dict[D_VERSION].size() > 1024 ||
       C.dict[D_GROUP].size() > 1024)
     throw NeedSequential();
   if (docs && C.dict[D_KEY].size() >= DN_MAX_KEYS) throw LimitError("too many distinct member names");
-  auto capbits = [](uint64_t m, const std::vector<uint32_t>& cm) {
-    uint64_t o = 0;
-    for (; m; m &= m - 1) o |= 1ull << cm[__builtin_ctzll(m)];
-    return o;
-  };
   for (size_t t = 0; t < T; ++t) {
-    const Corpus& P = parts[t];
+    const Corpus& P = *parts[t];
     for (size_t j = 0; j < P.capset_add.size(); ++j) {
       const uint64_t ad = capbits(P.capset_add[j], dmap[t][D_CAP]), dr = capbits(P.capset_drop[j], dmap[t][D_CAP]);
       std::string key(16, '\0');
@@ -2142,6 +2152,25 @@ void merge_parts(Corpus& C, std::vector<Corpus>& parts, bool docs, unsigned nthr
       capmap[t].push_back(cs);
     }
   }
+}
+
+// Concatenate per-chunk corpora (flattened in parallel, each with its own dictionaries) into
+// C. Parts are merged in document order, so every dictionary, scalar and capability-set id
+// is the one a sequential flatten assigns (first occurrence order).
+void merge_parts(Corpus& C, std::vector<Corpus>& parts, bool docs, unsigned nthreads) {
+  const size_t T = parts.size();
+  const auto tm0 = std::chrono::steady_clock::now();
+  // ---- id maps (sequential, document order) ----
+  IdMaps ids;
+  {
+    std::vector<const Corpus*> pp;
+    for (const Corpus& P : parts) pp.push_back(&P);
+    merge_ids(C, pp, docs, nthreads, ids);
+  }
+  const auto& dmap = ids.dmap;
+  const auto& capmap = ids.capmap;
+  const auto& scmap = ids.scmap;
+  const auto tm1 = std::chrono::steady_clock::now();
   // ---- bases of every part in the merged columns ----
   struct Base {
     size_t n, lab, ann, ctr, vol, sys, pann, port, doc;
@@ -2288,7 +2317,7 @@ void merge_parts(Corpus& C, std::vector<Corpus>& parts, bool docs, unsigned nthr
   C.n = (int64_t)e.n;
   if (getenv("KPE_DEBUG")) {
     const auto tm3 = std::chrono::steady_clock::now();
-    fprintf(stderr, "kpe merge: dictionaries %.3f s, capability sets + sizing %.3f s, placement %.3f s\n",
+    fprintf(stderr, "kpe merge: id maps %.3f s, sizing %.3f s, placement %.3f s\n",
             std::chrono::duration<double>(tm1 - tm0).count(), std::chrono::duration<double>(tm2 - tm1).count(),
             std::chrono::duration<double>(tm3 - tm2).count());
   }
@@ -2354,6 +2383,359 @@ void flatten_ndjson(Corpus& C, const char* buf, size_t len, const char* nsl, siz
     fprintf(stderr, "kpe flatten: %u threads, chunks %.3f s, merge %.3f s\n", T,
             std::chrono::duration<double>(t1 - t0).count(), std::chrono::duration<double>(t2 - t1).count());
   }
+}
+
+// ---- a corpus out of chosen rows of other corpora (kpe_corpus_gather) ----
+namespace {
+
+// a label table by namespace name, each entry a sorted set of (key, value) strings
+std::map<std::string, std::vector<std::pair<std::string, std::string>>> nsl_by_name(const Corpus& P) {
+  std::map<std::string, std::vector<std::pair<std::string, std::string>>> out;
+  const size_t nrows = P.nsl_off.size() - 1;
+  for (const auto& kv : P.nsl_index) {
+    auto& l = out[kv.first];
+    if (kv.second >= nrows) continue;
+    for (uint32_t j = P.nsl_off[kv.second]; j < P.nsl_off[kv.second + 1]; ++j)
+      l.emplace_back(std::string(P.dict[D_LABK].at(P.nsl_k[j])), std::string(P.dict[D_LABV].at(P.nsl_v[j])));
+    std::sort(l.begin(), l.end());
+    l.erase(std::unique(l.begin(), l.end()), l.end());
+  }
+  return out;
+}
+
+// the first tape entry of every row and the end of the last: a row's bodies, its root entry, then
+// its `images` bodies and root lie in one run (DocBuilder::add), and merges keep that layout.
+// Nothing else is on the tape: a walk that ends in DepthError is cut off again, and images() puts
+// its first entry only after its last throw, so an ImageError leaves no partial bodies behind
+std::vector<uint64_t> doc_starts(const Corpus& P) {
+  std::vector<uint64_t> s((size_t)P.n + 1, 0);
+  for (size_t r = 0; r < (size_t)P.n; ++r)
+    s[r + 1] = (P.img_off[r] != KPE_NO_IMAGES ? std::max(P.doc_off[r], P.img_off[r]) : P.doc_off[r]) + 1;
+  return s;
+}
+
+struct GatherAt {  // the columns' fill while rows are placed
+  uint64_t lab = 0, ann = 0, ctr = 0, vol = 0, sys = 0, pann = 0, port = 0, doc = 0;
+  void add(const GatherAt& o) {
+    lab += o.lab, ann += o.ann, ctr += o.ctr, vol += o.vol, sys += o.sys, pann += o.pann, port += o.port, doc += o.doc;
+  }
+};
+
+}  // namespace
+
+// C (empty) becomes the corpus of rows pairs[2k + 1] of srcs[pairs[2k]], k = 0 .. npairs: what a
+// flatten of those rows' lines in that order under the sources' label table gives every consumer.
+// The caller has checked the pairs against the sources' sizes. The sources' dictionaries, scalar
+// tables and capability sets are merged whole, in source order (merge_ids: the ids of a sequential
+// flatten when every row is listed in order); the table is source 0's. Throws std::invalid_argument
+// for sources that differ in documents or in their label tables (compared by namespace name, as
+// sets of pairs), LimitError when the merged tables cross a limit; C is then to be discarded.
+void gather_rows(Corpus& C, const std::vector<const Corpus*>& srcs, const uint64_t* pairs, uint64_t npairs) {
+  const size_t T = srcs.size();
+  const unsigned nth = flatten_threads();
+  if (!T) throw std::invalid_argument("kpe_corpus_gather: no source");
+  const bool docs = srcs[0]->has_docs;
+  for (const Corpus* P : srcs)
+    if (P->has_docs != docs) throw std::invalid_argument("kpe_corpus_gather: the sources differ in KPE_CORPUS_DOCS");
+  // ---- the label table: equal by name among the sources; source t's table row -> source 0's ----
+  std::vector<std::vector<uint32_t>> nslmap(T);
+  {
+    const auto t0 = nsl_by_name(*srcs[0]);
+    for (size_t t = 0; t < T; ++t) {
+      const Corpus& P = *srcs[t];
+      if (t && nsl_by_name(P) != t0)
+        throw std::invalid_argument("kpe_corpus_gather: the sources' namespace label tables differ");
+      nslmap[t].assign(P.nsl_off.size() - 1, KPE_NO_STR);
+      for (const auto& kv : P.nsl_index)
+        if (kv.second < nslmap[t].size()) nslmap[t][kv.second] = srcs[0]->nsl_index.at(kv.first);
+    }
+  }
+  if (npairs >= 0x7FFFFFC0ull) throw LimitError("more than 2^31 - 64 resources in one corpus (32-bit row ids)");
+  IdMaps ids;
+  try {
+    merge_ids(C, srcs, docs, nth, ids);
+  } catch (const NeedSequential&) {
+    throw LimitError("the merged dictionaries cross a limit the sources' rows were flattened under");
+  }
+  C.has_docs = docs;
+  {  // source 0's table, its label ids in the merged dictionaries
+    const Corpus& P = *srcs[0];
+    C.nsl_off = P.nsl_off, C.nsl_index = P.nsl_index;
+    C.nsl_k.resize(P.nsl_k.size()), C.nsl_v.resize(P.nsl_v.size());
+    for (size_t j = 0; j < P.nsl_k.size(); ++j)
+      C.nsl_k[j] = ids.dmap[0][D_LABK][P.nsl_k[j]], C.nsl_v[j] = ids.dmap[0][D_LABV][P.nsl_v[j]];
+  }
+  std::vector<std::vector<uint64_t>> dstart(T);
+  if (docs) parallel_for(T, nth, [&](size_t t) { dstart[t] = doc_starts(*srcs[t]); });
+  // ---- sizes: contiguous chunks of output rows, their totals, the chunks' bases ----
+  const size_t n = (size_t)npairs;
+  const size_t NC = std::max<size_t>(1, std::min<size_t>((n + 1023) / 1024, (size_t)nth * 4));
+  const size_t per = (n + NC - 1) / NC;
+  auto row_size = [&](size_t k) {
+    const size_t t = (size_t)pairs[2 * k], r = (size_t)pairs[2 * k + 1];
+    const Corpus& P = *srcs[t];
+    GatherAt s;
+    s.lab = P.lab_off[r + 1] - P.lab_off[r], s.ann = P.ann_off[r + 1] - P.ann_off[r];
+    s.ctr = P.ctr_off[r + 1] - P.ctr_off[r], s.vol = P.vol_off[r + 1] - P.vol_off[r];
+    s.sys = P.sys_off[r + 1] - P.sys_off[r], s.pann = P.pann_off[r + 1] - P.pann_off[r];
+    s.port = P.cport_off[P.ctr_off[r + 1]] - P.cport_off[P.ctr_off[r]];
+    if (docs) s.doc = dstart[t][r + 1] - dstart[t][r];
+    return s;
+  };
+  std::vector<GatherAt> base(NC + 1);
+  parallel_for(NC, nth, [&](size_t c) {
+    GatherAt s;
+    for (size_t k = c * per; k < std::min(n, (c + 1) * per); ++k) s.add(row_size(k));
+    base[c + 1] = s;
+  });
+  for (size_t c = 0; c < NC; ++c) base[c + 1].add(base[c]);
+  const GatherAt& e = base[NC];
+  if (e.doc > 0xFFFFFFFFull) throw LimitError("document tape exceeds 2^32 entries");
+  if (std::max({e.lab, e.ann, e.ctr, e.vol, e.sys, e.pann, e.port}) > 0xFFFFFFFFull)
+    throw LimitError("a list column exceeds 2^32 entries");
+  std::vector<std::function<void()>> sz;
+  for (auto* v : {&C.r_flags, &C.r_gvk, &C.r_name, &C.r_mns, &C.r_nsa, &C.r_nsl, &C.p_sc}) sz.push_back([v, n] { v->resize(n); });
+  sz.push_back([&] { C.p_cold.resize(n * 4); });
+  sz.push_back([&] { C.rec.resize(n * 4); });
+  for (auto* v : {&C.lab_off, &C.ann_off, &C.ctr_off, &C.vol_off, &C.sys_off, &C.pann_off})
+    sz.push_back([v, n] { v->resize(n + 1); });
+  for (auto* v : {&C.lab_k, &C.lab_v}) sz.push_back([v, &e] { v->resize(e.lab); });
+  for (auto* v : {&C.ann_k, &C.ann_v}) sz.push_back([v, &e] { v->resize(e.ann); });
+  sz.push_back([&] { C.vol_src.resize(e.vol); });
+  sz.push_back([&] { C.sys_id.resize(e.sys); });
+  for (auto* v : {&C.pann_k, &C.pann_v}) sz.push_back([v, &e] { v->resize(e.pann); });
+  sz.push_back([&] { C.pann_kv.resize(e.pann * 2); });
+  for (auto* v : {&C.c_sc, &C.c_name, &C.c_image, &C.c_sann, &C.c_sann_key, &C.c_sec_str, &C.c_pm_str, &C.c_selt_str,
+                  &C.c_selu_str, &C.c_selr_str})
+    sz.push_back([v, &e] { v->resize(e.ctr); });
+  sz.push_back([&] { C.c_add.resize(e.ctr); });
+  sz.push_back([&] { C.c_drop.resize(e.ctr); });
+  sz.push_back([&] { C.crec.resize(e.ctr * 2); });
+  sz.push_back([&] { C.cport_off.resize(e.ctr + 1); });
+  sz.push_back([&] { C.cport_host.resize(e.port); });
+  sz.push_back([&] { C.cport_str.resize(e.port); });
+  if (docs) {
+    sz.push_back([&] { C.doc.resize(e.doc * 2); });
+    sz.push_back([&] { C.doc_off.resize(n); });
+    sz.push_back([&] { C.img_off.resize(n); });
+  }
+  parallel_for(sz.size(), nth, [&](size_t i) { sz[i](); });
+  // ---- place every chunk's rows (parallel); each row as merge_parts places a part's ----
+  std::vector<std::vector<uint32_t>> limit(NC);
+  parallel_for(NC, nth, [&](size_t c) {
+    GatherAt o = base[c];
+    std::vector<uint32_t> stack;
+    for (size_t g = c * per; g < std::min(n, (c + 1) * per); ++g) {
+      const size_t t = (size_t)pairs[2 * g], r = (size_t)pairs[2 * g + 1];
+      const Corpus& P = *srcs[t];
+      const auto& M = ids.dmap[t];
+      auto id = [&](int d, uint32_t x) { return x == KPE_NO_STR ? x : M[d][x]; };
+      const GatherAt s = row_size(g);
+      const uint32_t gv = P.r_gvk[r];
+      const uint32_t gvk = M[D_KIND][GVK_KIND(gv)] | (M[D_VERSION][GVK_VER(gv)] << 12) | (M[D_GROUP][GVK_GRP(gv)] << 22);
+      C.r_flags[g] = P.r_flags[r], C.r_gvk[g] = gvk, C.r_name[g] = id(D_NAME, P.r_name[r]);
+      C.r_mns[g] = id(D_NS, P.r_mns[r]), C.r_nsa[g] = id(D_NS, P.r_nsa[r]);
+      C.r_nsl[g] = P.r_nsl[r] == KPE_NO_STR ? KPE_NO_STR : nslmap[t][P.r_nsl[r]];
+      if (P.r_flags[r] & (R_LIMIT | R_CTX_ERR)) limit[c].push_back((uint32_t)g);
+      C.p_sc[g] = P.p_sc[r];
+      for (int k = 0; k < 4; ++k) C.p_cold[g * 4 + k] = id(D_MISC, P.p_cold[r * 4 + k]);
+      C.rec[g * 4] = P.rec[r * 4], C.rec[g * 4 + 1] = gvk, C.rec[g * 4 + 2] = P.rec[r * 4 + 2];
+      C.rec[g * 4 + 3] = id(D_NS, P.rec[r * 4 + 3]);
+      C.lab_off[g + 1] = (uint32_t)(o.lab + s.lab), C.ann_off[g + 1] = (uint32_t)(o.ann + s.ann);
+      C.ctr_off[g + 1] = (uint32_t)(o.ctr + s.ctr), C.vol_off[g + 1] = (uint32_t)(o.vol + s.vol);
+      C.sys_off[g + 1] = (uint32_t)(o.sys + s.sys), C.pann_off[g + 1] = (uint32_t)(o.pann + s.pann);
+      for (size_t k = 0; k < s.lab; ++k) {
+        const size_t q = P.lab_off[r] + k;
+        C.lab_k[o.lab + k] = id(D_LABK, P.lab_k[q]), C.lab_v[o.lab + k] = id(D_LABV, P.lab_v[q]);
+      }
+      for (size_t k = 0; k < s.ann; ++k) {
+        const size_t q = P.ann_off[r] + k;
+        C.ann_k[o.ann + k] = id(D_ANNK, P.ann_k[q]), C.ann_v[o.ann + k] = id(D_ANNV, P.ann_v[q]);
+      }
+      for (size_t k = 0; k < s.vol; ++k) C.vol_src[o.vol + k] = P.vol_src[P.vol_off[r] + k];
+      for (size_t k = 0; k < s.sys; ++k) C.sys_id[o.sys + k] = id(D_SYSCTL, P.sys_id[P.sys_off[r] + k]);
+      for (size_t k = 0; k < s.pann; ++k) {
+        const size_t q = P.pann_off[r] + k;
+        const uint32_t ak = id(D_ANNK, P.pann_k[q]), av = id(D_ANNV, P.pann_v[q]);
+        C.pann_k[o.pann + k] = ak, C.pann_v[o.pann + k] = av;
+        C.pann_kv[(o.pann + k) * 2] = ak, C.pann_kv[(o.pann + k) * 2 + 1] = av;
+      }
+      const size_t c0 = P.ctr_off[r], p0 = P.cport_off[c0];
+      for (size_t k = 0; k < s.ctr; ++k) {
+        const size_t q = c0 + k, x = o.ctr + k;
+        C.c_sc[x] = P.c_sc[q];
+        C.c_add[x] = capbits(P.c_add[q], M[D_CAP]), C.c_drop[x] = capbits(P.c_drop[q], M[D_CAP]);
+        C.c_name[x] = id(D_CNAME, P.c_name[q]), C.c_image[x] = id(D_IMAGE, P.c_image[q]);
+        C.c_sann[x] = id(D_ANNV, P.c_sann[q]), C.c_sann_key[x] = id(D_ANNK, P.c_sann_key[q]);
+        C.c_sec_str[x] = id(D_MISC, P.c_sec_str[q]), C.c_pm_str[x] = id(D_MISC, P.c_pm_str[q]);
+        C.c_selt_str[x] = id(D_MISC, P.c_selt_str[q]), C.c_selu_str[x] = id(D_MISC, P.c_selu_str[q]);
+        C.c_selr_str[x] = id(D_MISC, P.c_selr_str[q]);
+        const uint32_t y = P.crec[q * 2 + 1];
+        C.crec[x * 2] = P.crec[q * 2], C.crec[x * 2 + 1] = ids.capmap[t][CY_CAPSET(y)] | (y & 0xFFFF0000u);
+        C.cport_off[x + 1] = (uint32_t)(o.port + (P.cport_off[q + 1] - p0));
+      }
+      for (size_t k = 0; k < s.port; ++k)
+        C.cport_host[o.port + k] = P.cport_host[p0 + k], C.cport_str[o.port + k] = id(D_MISC, P.cport_str[p0 + k]);
+      if (docs) {  // the row's run of the tape, walked from its roots: names and scalars remapped, bodies rebased
+        const auto& sm = ids.scmap[t];
+        const uint64_t d0 = dstart[t][r], d1 = dstart[t][r + 1];
+        const uint32_t delta = (uint32_t)(o.doc - d0);  // modulo 2^32: new index = old + delta
+        auto inside = [&](uint64_t en) {
+          if (en < d0 || en >= d1) throw std::logic_error("kpe_corpus_gather: a tape entry outside its row's run");
+        };
+        C.doc_off[g] = (uint32_t)P.doc_off[r] + delta;
+        stack.assign(1, (uint32_t)P.doc_off[r]);
+        C.img_off[g] = P.img_off[r] == KPE_NO_IMAGES ? KPE_NO_IMAGES : (uint64_t)((uint32_t)P.img_off[r] + delta);
+        if (P.img_off[r] != KPE_NO_IMAGES) stack.push_back((uint32_t)P.img_off[r]);
+        while (!stack.empty()) {
+          const uint32_t en = stack.back();
+          stack.pop_back();
+          inside(en);
+          const uint32_t x = P.doc[(size_t)en * 2], y = P.doc[(size_t)en * 2 + 1];
+          const uint32_t key1 = DN_KEY(x);
+          const size_t at = (size_t)(uint32_t)(en + delta) * 2;
+          C.doc[at] = DN_KIND(x) | ((key1 ? M[D_KEY][key1 - 1] + 1u : 0u) << 2);
+          if (DN_KIND(x) == DN_SCALAR) {
+            C.doc[at + 1] = sm[y];
+            continue;
+          }
+          inside(y);
+          C.doc[at + 1] = y + delta;
+          const uint32_t cnt = P.doc[(size_t)y * 2];
+          inside((uint64_t)y + cnt);
+          C.doc[(size_t)(uint32_t)(y + delta) * 2] = cnt, C.doc[(size_t)(uint32_t)(y + delta) * 2 + 1] = 0;
+          for (uint32_t q = 0; q < cnt; ++q) stack.push_back(y + 1 + q);
+        }
+      }
+      o.add(s);
+    }
+  });
+  for (auto& l : limit) C.limit_rows.insert(C.limit_rows.end(), l.begin(), l.end());
+  C.n = (int64_t)n;
+  rebuild_headers(C);
+}
+
+// One 64-bit digest per row that holds no id and no position (kpe_corpus_row_digests): every id
+// replaced by what it names, the tape walked from the row's two roots. A string stands by its
+// 64-bit hash (Dict::hash, which takes the length in), a scalar by a digest of its type, values
+// and texts, a capability mask by the sum of its names' hashes.
+void row_digests(const Corpus& C, uint64_t* out) {
+  const unsigned nth = flatten_threads();
+  std::vector<std::vector<uint64_t>> sh(KPE_NUM_DOMAINS);
+  parallel_for(KPE_NUM_DOMAINS, nth, [&](size_t d) {
+    sh[d].resize(C.dict[d].size());
+    for (uint32_t i = 0; i < C.dict[d].size(); ++i) sh[d][i] = Dict::hash(C.dict[d].at(i));
+  });
+  struct H {
+    uint64_t h = 0x9E3779B97F4A7C15ull;
+    void w(uint64_t x) {  // order-dependent: multiply-xorshift of the running value and the word
+      h = (h ^ x) * 0xff51afd7ed558ccdull;
+      h ^= h >> 32;
+      h *= 0xc4ceb9fe1a85ec53ull;
+      h ^= h >> 29;
+    }
+  };
+  auto str = [&](int d, uint32_t id) -> uint64_t { return id == KPE_NO_STR ? 0x6e6f2d737472ull : sh[d][id]; };
+  auto caps = [&](uint64_t m) {
+    uint64_t o = 0x63617073ull;
+    for (; m; m &= m - 1) o += sh[D_CAP][__builtin_ctzll(m)];
+    return o;
+  };
+  // scalars in table order: a range string's endpoints are earlier entries
+  std::vector<uint64_t> sd(C.scal.size());
+  for (size_t k = 0; k < C.scal.size(); ++k) {
+    const KpeScalar& e = C.scal[k];
+    H h;
+    uint64_t fb;
+    memcpy(&fb, &e.fval, 8);
+    h.w(e.flags), h.w(e.text_len), h.w(e.sp_len), h.w(fb), h.w((uint64_t)e.dur), h.w((uint64_t)e.qexp), h.w(e.qlo), h.w(e.qhi);
+    if ((e.flags & SC_RANGE) && SC_TYPE(e.flags) == SC_T_STR) {
+      const uint64_t x = (uint64_t)e.ival;
+      h.w(sd[(uint32_t)x]), h.w(sd[(uint32_t)(x >> 32)]);
+    } else {
+      h.w((uint64_t)e.ival);
+    }
+    const size_t nb = (size_t)e.text_len + e.sp_len;
+    if (nb) h.w(Dict::hash(std::string_view(C.scal_text.data() + e.text_off, nb)));
+    sd[k] = h.h;
+  }
+  // table rows: their label pairs as a set
+  std::vector<uint64_t> nd(C.nsl_off.size() - 1);
+  for (size_t i = 0; i < nd.size(); ++i) {
+    std::vector<std::pair<uint64_t, uint64_t>> kv;
+    for (uint32_t j = C.nsl_off[i]; j < C.nsl_off[i + 1]; ++j) kv.emplace_back(sh[D_LABK][C.nsl_k[j]], sh[D_LABV][C.nsl_v[j]]);
+    std::sort(kv.begin(), kv.end());
+    kv.erase(std::unique(kv.begin(), kv.end()), kv.end());
+    H h;
+    h.w(kv.size());
+    for (const auto& p : kv) h.w(p.first), h.w(p.second);
+    nd[i] = h.h;
+  }
+  const size_t n = (size_t)C.n, per = 4096;
+  parallel_for((n + per - 1) / per, nth, [&](size_t c) {
+    std::vector<uint32_t> stack;
+    for (size_t r = c * per; r < std::min(n, (c + 1) * per); ++r) {
+      H h;
+      const uint32_t gv = C.r_gvk[r];
+      h.w(C.r_flags[r]), h.w(sh[D_KIND][GVK_KIND(gv)]), h.w(sh[D_VERSION][GVK_VER(gv)]), h.w(sh[D_GROUP][GVK_GRP(gv)]);
+      h.w(str(D_NAME, C.r_name[r])), h.w(str(D_NS, C.r_mns[r])), h.w(str(D_NS, C.r_nsa[r]));
+      h.w(C.r_nsl[r] == KPE_NO_STR ? 0x6e6f2d6e736cull : nd[C.r_nsl[r]]);
+      h.w(C.lab_off[r + 1] - C.lab_off[r]);
+      for (uint32_t k = C.lab_off[r]; k < C.lab_off[r + 1]; ++k) h.w(str(D_LABK, C.lab_k[k])), h.w(str(D_LABV, C.lab_v[k]));
+      h.w(C.ann_off[r + 1] - C.ann_off[r]);
+      for (uint32_t k = C.ann_off[r]; k < C.ann_off[r + 1]; ++k) h.w(str(D_ANNK, C.ann_k[k])), h.w(str(D_ANNV, C.ann_v[k]));
+      h.w(C.p_sc[r]);
+      for (int k = 0; k < 4; ++k) h.w(str(D_MISC, C.p_cold[r * 4 + k]));
+      h.w(C.rec[r * 4]), h.w(C.rec[r * 4 + 2]), h.w(str(D_NS, C.rec[r * 4 + 3]));
+      h.w(C.vol_off[r + 1] - C.vol_off[r]);
+      for (uint32_t k = C.vol_off[r]; k < C.vol_off[r + 1]; ++k) h.w(C.vol_src[k]);
+      h.w(C.sys_off[r + 1] - C.sys_off[r]);
+      for (uint32_t k = C.sys_off[r]; k < C.sys_off[r + 1]; ++k) h.w(str(D_SYSCTL, C.sys_id[k]));
+      h.w(C.pann_off[r + 1] - C.pann_off[r]);
+      for (uint32_t k = C.pann_off[r]; k < C.pann_off[r + 1]; ++k) {
+        h.w(str(D_ANNK, C.pann_k[k])), h.w(str(D_ANNV, C.pann_v[k]));
+        h.w(str(D_ANNK, C.pann_kv[(size_t)k * 2])), h.w(str(D_ANNV, C.pann_kv[(size_t)k * 2 + 1]));
+      }
+      h.w(C.ctr_off[r + 1] - C.ctr_off[r]);
+      for (uint32_t k = C.ctr_off[r]; k < C.ctr_off[r + 1]; ++k) {
+        h.w(C.c_sc[k]), h.w(caps(C.c_add[k])), h.w(caps(C.c_drop[k]));
+        h.w(str(D_CNAME, C.c_name[k])), h.w(str(D_IMAGE, C.c_image[k]));
+        h.w(str(D_ANNV, C.c_sann[k])), h.w(str(D_ANNK, C.c_sann_key[k]));
+        h.w(str(D_MISC, C.c_sec_str[k])), h.w(str(D_MISC, C.c_pm_str[k])), h.w(str(D_MISC, C.c_selt_str[k]));
+        h.w(str(D_MISC, C.c_selu_str[k])), h.w(str(D_MISC, C.c_selr_str[k]));
+        const uint32_t y = C.crec[(size_t)k * 2 + 1], cs = CY_CAPSET(y);
+        h.w(C.crec[(size_t)k * 2]), h.w(y >> 16);
+        h.w(cs < C.capset_add.size() ? caps(C.capset_add[cs]) : 0), h.w(cs < C.capset_drop.size() ? caps(C.capset_drop[cs]) : 0);
+        h.w(C.cport_off[k + 1] - C.cport_off[k]);
+        for (uint32_t q = C.cport_off[k]; q < C.cport_off[k + 1]; ++q)
+          h.w((uint64_t)(int64_t)C.cport_host[q]), h.w(str(D_MISC, C.cport_str[q]));
+      }
+      if (C.has_docs) {  // depth first from each root, members in body order
+        for (int which = 0; which < 2; ++which) {
+          const uint64_t root = which ? C.img_off[r] : C.doc_off[r];
+          if (root == KPE_NO_IMAGES) {
+            h.w(0x6e6f2d696d67ull);
+            continue;
+          }
+          stack.assign(1, (uint32_t)root);
+          while (!stack.empty()) {
+            const uint32_t en = stack.back();
+            stack.pop_back();
+            const uint32_t x = C.doc[(size_t)en * 2], y = C.doc[(size_t)en * 2 + 1];
+            h.w(DN_KIND(x)), h.w(DN_KEY(x) ? sh[D_KEY][DN_KEY(x) - 1] : 0x6e6f2d6b6579ull);
+            if (DN_KIND(x) == DN_SCALAR) {
+              h.w(sd[y]);
+              continue;
+            }
+            const uint32_t cnt = C.doc[(size_t)y * 2];
+            h.w(cnt), h.w(C.doc[(size_t)y * 2 + 1]);
+            for (uint32_t q = cnt; q > 0; --q) stack.push_back(y + q);  // popped in body order
+          }
+        }
+      }
+      out[r] = h.h;
+    }
+  });
 }
 
 bool is_limit_error(const std::exception& e) { return dynamic_cast<const LimitError*>(&e) != nullptr; }

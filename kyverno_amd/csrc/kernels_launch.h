@@ -118,6 +118,15 @@ hipError_t kpe_launch_fp_pairs(const uint8_t* v, const uint32_t* masks, uint32_t
                                const uint64_t* tbl, uint32_t msg_codes, const uint64_t* kept, uint64_t* fp_out,
                                uint8_t* flags, hipStream_t s);
 
+// kept results gathered across corpora (kpe_results_gather). tab: the sources' base pointers, in
+// device memory; pairs: npairs x {source, row}, in device memory, every pair inside its source. out:
+// npairs x R bytes (4-byte aligned) / npairs words, row k = row pairs[2k + 1] of tab[pairs[2k]],
+// each byte written once. out overlaps no source.
+hipError_t kpe_launch_results_gather(const uint8_t* const* tab, const uint64_t* pairs, uint64_t npairs, uint32_t R,
+                                     uint8_t* out, hipStream_t s);
+hipError_t kpe_launch_fp_gather_pairs(const uint64_t* const* tab, const uint64_t* pairs, uint64_t npairs, uint64_t* out,
+                                      hipStream_t s);
+
 // report detail of a row list (kpe_fetch_report_rows) over the compact matrix v of `cells` cells
 // (a multiple of R). need: 3 R bytes, [mask][cond][pattern] in the KPE_SEL convention, bit 0
 // (KPE_NA) clear in every byte. tile_counts: 3 * ntiles words (+ padding to a multiple of four),

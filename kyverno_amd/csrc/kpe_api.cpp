@@ -32,6 +32,8 @@ void flatten_ndjson(Corpus& C, const char* buf, size_t len, const char* nsl, siz
 bool is_limit_error(const std::exception& e);
 uint64_t set_ns_labels(Corpus& C, const char* js, size_t len, bool replace, std::vector<uint32_t>* group_map);
 std::string ns_labels_json(const Corpus& C);
+void gather_rows(Corpus& C, const std::vector<const Corpus*>& srcs, const uint64_t* pairs, uint64_t npairs);
+void row_digests(const Corpus& C, uint64_t* out);
 }  // namespace kpe
 
 using kpe::DevBuf;
@@ -1754,6 +1756,32 @@ uint64_t kpe_corpus_digest(const kpe_corpus* c) {
   for (const KpeScalar& e : C.scal) mix(&e, sizeof(e));
   return h;
 }
+kpe_status kpe_corpus_gather(const kpe_corpus* const* srcs, int nsrcs, const uint64_t* pairs, uint64_t npairs,
+                             kpe_corpus** out) {
+  if (!out) return fail(KPE_E_INVALID, "kpe_corpus_gather: null argument");
+  if (kpe_status st = kpe::gather_args("kpe_corpus_gather", srcs, nsrcs, pairs, npairs, nullptr)) return st;
+  std::vector<const kpe::Corpus*> cs;
+  for (int t = 0; t < nsrcs; ++t) cs.push_back(srcs[t]->c.get());
+  auto c = std::make_unique<kpe::Corpus>();
+  try {
+    kpe::gather_rows(*c, cs, pairs, npairs);
+  } catch (const std::exception& e) {
+    return fail(kpe::is_limit_error(e) ? KPE_E_LIMIT : KPE_E_INVALID, e.what());
+  }
+  *out = new kpe_corpus{std::move(c), nullptr};
+  return KPE_OK;
+}
+
+kpe_status kpe_corpus_row_digests(const kpe_corpus* c, uint64_t* out) {
+  if (!c || (c->c->n && !out)) return fail(KPE_E_INVALID, "kpe_corpus_row_digests: null argument");
+  try {
+    kpe::row_digests(*c->c, out);
+  } catch (const std::exception& e) {
+    return fail(KPE_E_INVALID, e.what());
+  }
+  return KPE_OK;
+}
+
 void kpe_corpus_free(kpe_corpus* c) {
   if (!c) return;
   if (c->d) (void)hipSetDevice(c->d->ordinal);

@@ -11,6 +11,8 @@
 //  kpe_delta_*_kernel, kpe_gather_rows_kernel — result deltas against a kept matrix.
 //  kpe_splice_kernel     — a policy edit's columns spliced into the kept matrix (kpe_results_splice).
 //  kpe_row_fp_kernel, kpe_fp_diff_kernel, kpe_fp_gather_kernel — row fingerprints and their compare.
+//  kpe_results_gather_kernel, kpe_fp_gather_pairs_kernel — kept rows of several corpora gathered into
+//                          another's kept matrix / fingerprints (kpe_results_gather).
 //  kpe_report_need_count_kernel, kpe_report_need_scatter_kernel, kpe_fe_words_gather_kernel — the
 //                          report detail of a row list (check mask words, condition trace words,
 //                          pattern cells).
@@ -913,6 +915,47 @@ extern "C" hipError_t kpe_launch_fp_pairs(const uint8_t* v, const uint32_t* mask
   else
     hipLaunchKernelGGL(kpe_fp_pairs_kernel<false>, grid, dim3(256), dyn, s, v, masks, R, pairs, npairs, tbl, lds, msg_codes,
                        kept, fp_out, flags);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Kept results carried into a gathered corpus (kpe_results_gather): output row k is row pairs[2k + 1]
+// of source pairs[2k], the sources' base pointers in a device table (gather.inl, shared with
+// scripts/corpus_gather_check.cpp). One contiguous byte range of the output per block, whole words
+// between its aligned ends, byte stores for the matrix's last partial word; no atomics, no zeroing pass.
+#define KPE_GA_FN __host__ __device__ __forceinline__
+#define KPE_GA_DEV __device__ __forceinline__
+namespace {
+__device__ __forceinline__ uint32_t ga_load4(const uint8_t* p) { return *reinterpret_cast<const uint32_t*>(p); }
+__device__ __forceinline__ void ga_store4(uint8_t* p, uint32_t w) { *reinterpret_cast<uint32_t*>(p) = w; }
+#include "gather.inl"
+}  // namespace
+
+__global__ void __launch_bounds__(256) kpe_results_gather_kernel(const uint8_t* const* __restrict__ tab,
+                                                                 const uint64_t* __restrict__ pairs, uint64_t total,
+                                                                 uint32_t R, uint8_t* __restrict__ out) {
+  const GaRange G = ga_range(total, gridDim.x, blockIdx.x);
+  ga_copy(G, threadIdx.x, tab, pairs, R, out);
+}
+__global__ void __launch_bounds__(256) kpe_fp_gather_pairs_kernel(const uint64_t* const* __restrict__ tab,
+                                                                  const uint64_t* __restrict__ pairs, uint64_t npairs,
+                                                                  uint64_t* __restrict__ out) {
+  for (uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x; k < npairs; k += (uint64_t)gridDim.x * 256u)
+    ga_fp(k, tab, pairs, out);
+}
+extern "C" hipError_t kpe_launch_results_gather(const uint8_t* const* tab, const uint64_t* pairs, uint64_t npairs,
+                                                uint32_t R, uint8_t* out, hipStream_t s) {
+  const uint64_t total = npairs * R;
+  if (!total) return hipSuccess;
+  if (((uintptr_t)out & 3u) != 0u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kpe_results_gather_kernel, dim3(ga_grid(total)), dim3(kGaLanes), 0, s, tab, pairs, total, R, out);
+  return hipGetLastError();
+}
+extern "C" hipError_t kpe_launch_fp_gather_pairs(const uint64_t* const* tab, const uint64_t* pairs, uint64_t npairs,
+                                                 uint64_t* out, hipStream_t s) {
+  if (!npairs) return hipSuccess;
+  const dim3 grid((unsigned)std::min<uint64_t>((npairs + 255u) / 256u, 1u << 16));
+  hipLaunchKernelGGL(kpe_fp_gather_pairs_kernel, grid, dim3(256), 0, s, tab, pairs, npairs, out);
   return hipGetLastError();
 }
 

@@ -170,6 +170,41 @@ class Corpus:
         self.nbytes = int(L.kpe_corpus_bytes(h))
         self.device = None
 
+    @staticmethod
+    def _gather_args(srcs, pairs):
+        srcs = list(srcs)
+        p = np.ascontiguousarray(pairs, dtype=np.uint64).reshape(-1, 2)
+        hs = (ctypes.c_void_p * max(len(srcs), 1))(*[s.h for s in srcs])
+        return srcs, p, hs
+
+    @classmethod
+    def gather(cls, srcs: Sequence["Corpus"], pairs) -> "Corpus":
+        """A corpus out of chosen rows of other corpora (kpe_corpus_gather): pairs is (k, 2) of
+        (index into srcs, row), and row k of the result is that row. No JSON is read; every
+        consumer behaves as on a corpus flattened from those rows' lines in that order under the
+        sources' namespace label table. The result is not uploaded, has nothing retired and keeps
+        nothing. KpeError 1 (KPE_E_INVALID) for a pair outside its source or naming a retired row
+        and for sources that differ in documents or label tables; 4 (KPE_E_LIMIT) when the merged
+        dictionaries cross a limit: flatten the lines again."""
+        L = load()
+        srcs, p, hs = cls._gather_args(srcs, pairs)
+        h = ctypes.c_void_p()
+        check(L.kpe_corpus_gather(hs if srcs else None, len(srcs), p.ctypes.data if p.size else None, len(p),
+                                  ctypes.byref(h)))
+        self = cls.__new__(cls)
+        self.h = h
+        self.n = int(L.kpe_corpus_num_resources(h))
+        self.nbytes = int(L.kpe_corpus_bytes(h))
+        self.device = None
+        return self
+
+    def row_digests(self) -> np.ndarray:
+        """One uint64 per row that holds no id and no position (kpe_corpus_row_digests): equal for
+        two rows flattened from the same line under the same label table, in whatever corpus."""
+        out = np.zeros(self.n, dtype=np.uint64)
+        check(load().kpe_corpus_row_digests(self.h, out.ctypes.data if self.n else None))
+        return out
+
     def row_flags(self) -> np.ndarray:
         """Per-row flatten status (kpe_corpus_row_flags): KPE_ROW_DECODE_ERROR = 1,
         KPE_ROW_LIMIT = 2, KPE_ROW_NO_SPEC = 4."""
@@ -629,6 +664,16 @@ class Engine:
 
     def drop_fingerprints(self, corpus: Corpus):
         check(load().kpe_fingerprints_drop(self.device.h, corpus.h))
+
+    def gather_results(self, dst: Corpus, srcs: Sequence[Corpus], pairs, what: int = 0):
+        """Carry kept results into a gathered corpus on the device (kpe_results_gather): dst
+        (uploaded, one row per pair, as Corpus.gather(srcs, pairs) makes it) receives the kept
+        matrix rows (GATHER_MATRIX) and / or kept fingerprints (GATHER_FINGERPRINTS) of the listed
+        rows of srcs; what=0: whatever every listed source keeps. Nothing is evaluated and nothing
+        crosses to the host."""
+        srcs, p, hs = Corpus._gather_args(srcs, pairs)
+        check(load().kpe_results_gather(self.device.h, dst.h, hs if srcs else None, len(srcs),
+                                        p.ctypes.data if p.size else None, len(p), what))
 
     def changed_rows_fp(self, ps: PolicySet, corpus: Corpus, salts=None, msg_salts=None, msg_codes=None, masks=False,
                         cap: Optional[int] = None, with_verdicts=True):
@@ -1198,6 +1243,7 @@ def splice_bytes(n: int, Ro: int, Rs: int, rn: int) -> float:
     return float(load().kpe_splice_bytes(n, Ro, Rs, rn))
 
 
+GATHER_MATRIX, GATHER_FINGERPRINTS = 1, 2  # include/kpe.h KPE_GATHER_*: what Engine.gather_results carries
 FP_MASKS = 1  # include/kpe.h KPE_FP_MASKS: FAIL cells' check mask words count
 NSL_REPLACE = 1  # include/kpe.h KPE_NSL_REPLACE: the JSON is the whole namespace label table
 MESSAGE_CODES = SEL(2) | SEL(4) | SEL(5)  # FAIL, ERROR, SKIP: results whose message the policy text decides

@@ -362,6 +362,7 @@ class ResidentScanner:
         self._keyed = bool(keyed)
         self._ns_objects = bool(ns_objects)
         self._stale = False  # keyed: rows were retired since the segments' last evaluation
+        self._unevaluated = False  # keyed: the segment was gathered (compact) and not evaluated since
         self._lines = ndjson_rows(ndjson) if (reports or keyed) else None  # logical row i is line i
         self._segs = [self.corpus]  # keyed: the segments (RowMap); segment 0 is self.corpus
         self._map = None
@@ -482,7 +483,7 @@ class ResidentScanner:
         every rescan): labels is {namespace: {key: value}, or None to remove the entry}, a patch by
         default, the whole table with replace=True (Engine.set_namespace_labels). The table of every
         segment is replaced in place, on the device; the corpus, its upload, the kept results and
-        the retired rows stay, and later delta segments and `compact` flatten with the new table.
+        the retired rows stay, later delta segments flatten with the new table and `compact` carries it.
 
         With a PolicySet applied, returns {row: verdict row} of exactly the rows whose report
         changes: the segments are evaluated again and compared with the kept result as `apply`
@@ -521,7 +522,7 @@ class ResidentScanner:
             raise KpeError(5, "no apply yet")  # KPE_E_STATE
         if self._stale:
             self.engine.evaluate_batch_async(self._applied, self._segs, masks=self._with_reports)
-            self._stale, self._edit = False, None
+            self._stale, self._edit, self._unevaluated = False, None, False
 
     def namespace_counts(self):
         """Per-namespace rule counts of the resident corpus under the last applied PolicySet:
@@ -569,7 +570,7 @@ class ResidentScanner:
                 raise KpeError(5, 'reports(policies="edited"): only right after an apply_edit')
             ps = self._edit
         else:
-            if self._edit is not None:  # the segments' last evaluation is of the edited policies alone
+            if self._edit is not None or self._unevaluated:  # the last evaluation is of the edited policies alone, or none
                 self._refresh()
             ps = self._applied
         rows = [int(i) for i in rows]
@@ -598,7 +599,8 @@ class ResidentScanner:
 
         full: the complete new PolicySet, or a zero-argument callable returning it, called only when
         something needs the whole set (namespace_counts, cli_summary, reports, matrix, update,
-        set_namespace_labels, compact, which evaluate it first). Rules are paired by name, so the
+        set_namespace_labels, compact(reflatten=True), which evaluate it first; a compaction by
+        gather leaves it alone). Rules are paired by name, so the
         rules of `edited` must carry the names they have in `full`.
 
         keep="matrix" only: keep="fingerprints" raises ValueError, since a fingerprint cannot give
@@ -646,7 +648,7 @@ class ResidentScanner:
         eng, m = self.engine, self._map
         eng.evaluate_batch_async(policies, self._segs, masks=self._with_reports)
         self._applied = policies
-        self._stale, self._edit = False, None
+        self._stale, self._edit, self._unevaluated = False, None, False
         out = {}
         for s, seg in enumerate(self._segs):
             if msg is not None:
@@ -765,13 +767,50 @@ class ResidentScanner:
             self.last_stats["compacted"] = True
         return out
 
-    def compact(self):
-        """Re-flatten the live rows into one segment in logical order, evaluate the last applied
-        PolicySet on it and keep that result; with keep="fingerprints" the kept fingerprints are
-        carried over (Engine.load_fingerprints). The recompute reports nothing as changed: it is
-        the state the segments already held."""
+    def compact(self, reflatten=False):
+        """One segment again: the live rows in logical order. The segments are flattened already,
+        so the new one is gathered from their rows (Corpus.gather: no JSON is parsed), uploaded,
+        and the kept matrix or fingerprints of those rows are carried over on the device
+        (Engine.gather_results). Nothing is compiled or evaluated, no fingerprint crosses to the
+        host and a lazy `full` of apply_edit stays unresolved; the readers that need an evaluation
+        of the applied set (matrix, reports, namespace_counts, cli_summary) evaluate first, as
+        they do after rows were retired. Nothing is reported as changed: it is the state the
+        segments already held.
+
+        reflatten=True, or merged dictionaries past a limit the rows were flattened under
+        (KPE_E_LIMIT): the live NDJSON lines are flattened again instead, the last applied
+        PolicySet is evaluated on the result and that is kept; with keep="fingerprints" the kept
+        fingerprints are carried over through the host (Engine.load_fingerprints)."""
         self._need_keyed()
         eng, m = self.engine, self._map
+        if not reflatten:
+            live = m.live()
+            pairs = np.array([m.loc[l] for l in live], dtype=np.uint64).reshape(-1, 2)
+            try:
+                seg = Corpus.gather(self._segs, pairs)
+            except KpeError as e:
+                if e.status != 4:  # KPE_E_LIMIT: flatten again
+                    raise
+                seg = None
+            if seg is not None:
+                seg.upload(eng.device)
+                if self.keep == "fingerprints":
+                    # loaded fingerprints and an update before the first apply: the delta segments keep
+                    # nothing. Their rows stand against "no report" (0), as in _apply_segments, so that
+                    # every segment keeps fingerprints and the loaded ones are carried.
+                    has = [eng.kept_fingerprints(s, 0, 0) is not None for s in self._segs]
+                    if any(has) and not all(has):
+                        for s, h in zip(self._segs, has):
+                            if not h:
+                                eng.load_fingerprints(s, np.zeros(s.n, dtype=np.uint64))
+                eng.gather_results(seg, self._segs, pairs)
+                m.compact()
+                self._segs = [seg]
+                self.corpus = seg
+                self._edit = None
+                self._stale = self._unevaluated = self._applied_v is not None
+                self._updated = True
+                return
         fps = self._fps_by_row() if self.keep == "fingerprints" else None
         had_fps = fps is not None and eng.kept_fingerprints(self._segs[0], 0, 0) is not None
         live = m.compact()
@@ -780,7 +819,7 @@ class ResidentScanner:
             raise KpeError(2, "compact: one corpus row per live resource")  # KPE_E_INVALID
         self._segs = [seg]
         self.corpus = seg
-        self._stale, self._edit = False, None
+        self._stale, self._edit, self._unevaluated = False, None, False
         if self._applied is not None:
             eng.evaluate_async(self._applied, seg, masks=self._with_reports)
             if self.keep != "fingerprints":
@@ -796,7 +835,7 @@ class ResidentScanner:
         self._need_keyed()
         if self._applied_v is None:
             raise KpeError(5, "no apply yet")
-        if self._edit is not None:  # the segments' last evaluation is of the edited policies alone
+        if self._edit is not None or self._unevaluated:  # the last evaluation is of the edited policies alone, or none
             self._refresh()
         out = np.zeros((self._map.n_logical, self._applied.num_rules), dtype=np.uint8)
         for s, seg in enumerate(self._segs):
